@@ -6,8 +6,12 @@ Workload of the headline `value` (BASELINE.json configs[1]): 1080p synthetic lum
 full-search integer ME with range 16 (33x33 = 1089 16x16 SAD candidates per MB,
 8160 MBs per frame), one step = one x264hip_8_me_search_full launch over
 `--frames` (fenc, ref) pairs already resident in HBM.  value = candidates/s over
-all ranks.  Side rates of configs[2] (SATD 8x8 candidates, fused 4x4 and 8x8
-DCT+quant blocks) are measured in the same run and reported under "extra".
+all ranks.  A plain run sets up, warms up, times `--steps` steps and prints the
+result line.  With `--full` the side rates of configs[2] (SATD 8x8 candidates,
+fused 4x4 and 8x8 DCT+quant blocks, ...) are measured in the same run and reported
+under "extra", and the oracle's rates on the host cores under "cpu_baseline".
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy
+(the inputs are seeded, so two builds can be compared output for output).
 
 Multi-GPU: one process per GPU (torchrun), frames are sharded by rank (every
 rank owns its own frame pairs: weak scaling, no data-path collective); the
@@ -164,34 +168,50 @@ def workload_2160p(x, a, world, rank, pg_world, rank_dev):
     cur_stream = torch.cuda.current_stream()
     wall, _ = timed(step, a.steps, a.warmup, world)
     cur_stream.wait_stream(comp)
-    # the parts alone: the upload (both planes) and the compute of one frame
-    reset()
-    with torch.cuda.stream(copy):
-        _, up_ms = timed(lambda: upload(1, 1), a.steps, min(a.warmup, 20), world)
-    with torch.cuda.stream(comp):
-        _, comp_ms = timed(lambda: frame(1, 0), a.steps, min(a.warmup, 20), world)
-    # host time to enqueue one step (no GPU wait inside step())
-    reset()
-    t0 = time.perf_counter()
-    for _ in range(a.steps):
-        step()
-    host_ms = (time.perf_counter() - t0) / a.steps * 1e3
     torch.cuda.synchronize()
     value = world * a.steps * cand_frame / wall
-    # the dominant kernel alone (the fused search + decision of one 2160p frame) on the compute
-    # stream's 240 CUs, events on that stream
-    with torch.cuda.stream(comp):
-        _, s_ms = timed(lambda: esa(ring[1:2], ring[0:1]), a.steps, a.warmup, world)
-    torch.cuda.synchronize()
-    x.stream_pair_destroy((comp, copy))
-    absd = nmb * (2 * R + 1) ** 2 * 256
-    roof = {"kernel": "me_full_esa_v7_kernel<%d, false>" % R, "bound": "valu",
-            "achieved": absd / (s_ms * 1e-3) / 1e12, "peak": SAD_PEAK_ABSDIFF / 1e12,
-            "unit": "T byte-absdiff/s (algorithmic: 256 per 16x16 candidate)",
-            "frac": absd / (s_ms * 1e-3) / SAD_PEAK_ABSDIFF, "traffic": None, "launch_ms": s_ms,
-            "cus": 240, "peak_note": "peak is the whole chip's 256 CUs; the kernel runs on the compute stream's 240",
-            "algorithmic_bytes_per_launch": 2 * nmb * 256 + nmb * 12}
     ms = wall / a.steps * 1e3
+    if a.dump_outputs:
+        # what the last step's frame() left: the ESA decision (cost, mx, my), the refine's result
+        # and its call counts, the 4x4 coefficients and nz flags; every MB, or a seeded sample
+        rows = sample_rows(nmb, DUMP_LIMIT // world // (256 * 4 + 10 * 8))
+        sel = torch.from_numpy(rows).cuda()
+        dump_outputs(a.dump_outputs, rank, {"esa_decision": dec[sel].cpu().numpy(),
+                                            "refine_result": rout[sel].cpu().numpy(),
+                                            "refine_nevals": ne[sel].cpu().numpy(),
+                                            "dct4_coefs": dct[sel].cpu().numpy(), "dct4_nz": nz[sel].cpu().numpy(),
+                                            "mb_index": rows})
+    parts, roof = {}, None
+    if a.full:
+        # the parts alone: the upload (both planes) and the compute of one frame
+        reset()
+        with torch.cuda.stream(copy):
+            _, up_ms = timed(lambda: upload(1, 1), a.steps, min(a.warmup, 20), world)
+        with torch.cuda.stream(comp):
+            _, comp_ms = timed(lambda: frame(1, 0), a.steps, min(a.warmup, 20), world)
+        # host time to enqueue one step (no GPU wait inside step())
+        reset()
+        t0 = time.perf_counter()
+        for _ in range(a.steps):
+            step()
+        host_ms = (time.perf_counter() - t0) / a.steps * 1e3
+        torch.cuda.synchronize()
+        parts = {"upload_ms": up_ms, "upload_GBps": up_bytes / (up_ms * 1e-3) / 1e9, "compute_ms": comp_ms,
+                 "host_enqueue_ms": host_ms, "step_vs_upload": ms / up_ms}
+        # the dominant kernel alone (the fused search + decision of one 2160p frame) on the compute
+        # stream's 240 CUs, events on that stream
+        with torch.cuda.stream(comp):
+            _, s_ms = timed(lambda: esa(ring[1:2], ring[0:1]), a.steps, a.warmup, world)
+        torch.cuda.synchronize()
+        absd = nmb * (2 * R + 1) ** 2 * 256
+        roof = {"kernel": "me_full_esa_v7_kernel<%d, false>" % R, "bound": "valu",
+                "achieved": absd / (s_ms * 1e-3) / 1e12, "peak": SAD_PEAK_ABSDIFF / 1e12,
+                "unit": "T byte-absdiff/s (algorithmic: 256 per 16x16 candidate)",
+                "frac": absd / (s_ms * 1e-3) / SAD_PEAK_ABSDIFF, "traffic": None, "launch_ms": s_ms,
+                "cus": 240,
+                "peak_note": "peak is the whole chip's 256 CUs; the kernel runs on the compute stream's 240",
+                "algorithmic_bytes_per_launch": 2 * nmb * 256 + nmb * 12}
+    x.stream_pair_destroy((comp, copy))
     out = {
         "metric": "SAD+SATD candidate-MVs/sec + DCT+quant blocks/sec, 1080p, 1/2/4/8 GPU",
         "value": value,
@@ -207,14 +227,13 @@ def workload_2160p(x, a, world, rank, pg_world, rank_dev):
                    "candidates_per_mb": cand_frame / nmb, "table_candidates_per_mb": (2 * R + 1) ** 2,
                    "refine_candidates_per_frame": float(np.mean(rcands)),
                    "refine_chroma_calls_per_frame": float(np.mean(rchroma)),
-                   "refine_moved_frac": float(np.mean(moved)), "upload_bytes_per_frame": int(up_bytes),
-                   "upload_ms": up_ms, "upload_GBps": up_bytes / (up_ms * 1e-3) / 1e9, "compute_ms": comp_ms,
-                   "host_enqueue_ms": host_ms, "step_vs_upload": ms / up_ms,
+                   "refine_moved_frac": float(np.mean(moved)), "upload_bytes_per_frame": int(up_bytes), **parts,
                    "parallelism": "frame-per-GPU x%d" % world, "world_size": pg_world, "rank_devices": rank_dev,
                    "dist_backend": (os.environ.get("X264HIP_DIST_BACKEND", "nccl") if world > 1 else None)},
-        "roofline": roof,
     }
-    if rank == 0 and world == 1 and not a.no_cpu:
+    if roof is not None:
+        out["roofline"] = roof
+    if a.full and rank == 0 and world == 1 and not a.no_cpu:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import oracle_lib as orc  # cpu_baseline leg only
         f0 = ring[1].cpu().numpy().ravel()
@@ -266,8 +285,13 @@ def parse():
     # configs[1] (the default headline) or configs[3]: a 2160p frame per GPU per step, full search +
     # refine_subpel + DCT/quant, the new frame streamed from pinned host memory (workload_2160p)
     ap.add_argument("--workload", choices=("1080p", "2160p"), default="1080p")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-extra", action="store_true", help="skip the configs[2] side rates")
+    # a plain run measures the headline only; --full adds every other leg (side rates, the parts
+    # of the 2160p step alone, steady-state and roofline re-runs, cpu_baseline)
+    ap.add_argument("--full", action="store_true", help="also run the side-rate, roofline and cpu_baseline legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline leg")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the configs[2] side rates")
     ap.add_argument("--cpu-seconds", type=float, default=1.5, help="wall-clock bound of the CPU sample")
     return ap.parse_args()
 
@@ -385,6 +409,31 @@ def _timed_graph(fn, steps, warmup, world):
     return max_over_ranks(t1 - t0, world), ev_ms
 
 
+# --dump-outputs: bytes of array data one run may write (under 64 MB with the .npy headers)
+DUMP_LIMIT = 60 * 1000 * 1000
+
+
+def sample_rows(n, limit, seed=11):
+    """Sorted indices of the rows a dump keeps: all n, or a fixed (seeded) sample of `limit`."""
+    if n <= limit:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.Generator(np.random.PCG64(seed)).choice(n, size=limit, replace=False))
+
+
+def dump_outputs(dirname, rank, arrays):
+    """Write each array as DIR/<name>.npy (rank r > 0: <name>.rank<r>.npy): 8- and 16-bit
+    integers as float32, wider ones as float64, both exact."""
+    os.makedirs(dirname, exist_ok=True)
+    total = 0
+    for name, arr in arrays.items():
+        arr = np.asarray(arr)
+        arr = np.ascontiguousarray(arr, dtype=np.float32 if arr.dtype.itemsize <= 2 else np.float64)
+        total += arr.nbytes
+        if total > DUMP_LIMIT:
+            raise SystemExit("bench: --dump-outputs would write more than %d bytes" % DUMP_LIMIT)
+        np.save(os.path.join(dirname, name + ("" if rank == 0 else ".rank%d" % rank) + ".npy"), arr)
+
+
 def world_devices(world):
     """(process-group world size, the device id of every rank) for the JSON line."""
     dev = torch.cuda.current_device()
@@ -444,6 +493,14 @@ def main():
     cands = world * a.steps * F * mbw * mbh * cand_per_mb
     value = cands / wall
     ms_per_step = wall / a.steps * 1e3
+    if a.dump_outputs:
+        # the last step's SAD tables (u16 costs, the pitch's padding columns dropped): every MB's
+        # table, or a fixed seeded sample of the MBs with their indices into [F, mbh, mbw]
+        rows = sample_rows(F * mbh * mbw, DUMP_LIMIT // world // (cand_per_mb * 4 + 8))
+        got = table.view(-1, 2 * R + 1, x.me_table_pitch(R))[torch.from_numpy(rows).cuda()]
+        dump_outputs(a.dump_outputs, rank, {"me_table": got.cpu().numpy().view(np.uint16)[..., :2 * R + 1],
+                                            "me_table_mb_index": rows})
+        del got
     global _SETTLE_S
     _SETTLE_S = 0.04
 
@@ -501,7 +558,7 @@ def main():
         "roofline": roof,
     }
 
-    if not a.no_extra:
+    if a.full and not a.no_extra:
         XF = min(a.xframes, F)
         out["extra"] = extra_rates(x, a, world, dev[:XF + 1], origin, stride, fstride, mbw, mbh, XF, full=dev)
         # the headline kernel again after the extra legs have kept the GPU busy for tens of
@@ -510,7 +567,7 @@ def main():
         _, ss_ms = timed(step, a.steps, 10, world)
         out["extra"]["me_steady_launch_ms"] = ss_ms
         out["extra"]["me_steady_frac"] = absdiff_per_launch / (ss_ms * 1e-3) / SAD_PEAK_ABSDIFF
-    if rank == 0 and world == 1 and not a.no_cpu:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu:
         out["cpu_baseline"] = cpu_baseline(planes, origin, stride, mbw, mbh, R, a.cpu_seconds)
     if rank == 0:
         print(json.dumps(out))

@@ -1,6 +1,7 @@
-"""bench.py's one-line JSON contract on the GPU (short run: 2 timed steps, headline only,
-a 0.3-s CPU sample): the keys the driver and the judge read, their types and the
-consistency of the roofline record with the line's own numbers."""
+"""bench.py's one-line JSON contract on the GPU (short run: 2 timed steps, --full without the
+side rates, a 0.3-s CPU sample): the keys the driver and the judge read, their types and the
+consistency of the roofline record with the line's own numbers; a plain run's line and its
+--dump-outputs files."""
 import json
 import os
 import subprocess
@@ -13,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.gpu
 def test_bench_json_contract():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1",
                         "--frames", "8", "--no-extra", "--cpu-seconds", "0.3"],
                        capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -40,6 +41,40 @@ def test_bench_json_contract():
     for k in ("value", "unit", "cores", "kind", "sample"):
         assert k in cb, k
     assert cb["kind"] == "port" and cb["value"] > 0 and cb["cores"] >= 1
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_and_dump(tmp_path, oracle):
+    """A plain run (no --full) times the headline only: no side rates, no cpu_baseline; and
+    --dump-outputs writes the last step's SAD tables, here every MB of a 2-pair 96x48 run,
+    equal to the oracle's full search of the same seeded frames."""
+    import numpy as np
+    from conftest import load_package
+    load_package()
+    from x264hip import synth
+    w, h, rng, f = 96, 48, 8, 2
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--frames", str(f), "--width", str(w), "--height", str(h), "--range", str(rng),
+                        "--dump-outputs", str(tmp_path / "out")],
+                       capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline"):
+        assert k in d, k
+    assert "extra" not in d and "cpu_baseline" not in d
+    assert d["steps"] == 2 and d["value"] > 0 and d["ms_per_step"] > 0
+    assert sorted(os.listdir(tmp_path / "out")) == ["me_table.npy", "me_table_mb_index.npy"]
+    got = np.load(tmp_path / "out" / "me_table.npy")
+    idx = np.load(tmp_path / "out" / "me_table_mb_index.npy")
+    mbw, mbh = w // 16, h // 16
+    assert got.dtype == np.float32 and idx.dtype == np.float64
+    assert np.array_equal(idx, np.arange(f * mbw * mbh))
+    planes, stride, origin = synth.make_sequence(f + 1, w, h, 8)
+    want = np.stack([oracle.me_search_full(8, planes[k + 1].ravel(), origin, stride, planes[k].ravel(), origin,
+                                           stride, mbw, mbh, rng) for k in range(f)])
+    assert np.array_equal(got, want.reshape(got.shape).astype(np.float32))
 
 
 @pytest.mark.gpu
@@ -80,7 +115,7 @@ def test_bench_2160p_workload(gpus):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "2160p", "--gpus", str(gpus),
-                        "--steps", "3", "--warmup", "2", "--cpu-seconds", "0.3"],
+                        "--full", "--steps", "3", "--warmup", "2", "--cpu-seconds", "0.3"],
                        capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

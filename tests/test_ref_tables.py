@@ -1,14 +1,15 @@
 """CPU: the constant tables the oracle and the product restate, pinned to the reference's
 own text.  Parity of the arithmetic stays unpinned (the reference
 cannot be built here), but every table both sides copied from it is
-checked value for value against the reference source, read as text:
+checked value for value against the reference source's numbers, recorded from its text in
+tests/golden/ref_tables.json (tests/golden/make_ref_tables.py):
 
 * common/set.c:31-71        dequant4/8_scale, quant4/8_scale, quant8_scan
 * common/tables.c:183-184   x264_hpel_ref0 / x264_hpel_ref1
 * encoder/me.c:53-56        mod6m1, hex2, square1
 * common/dct.c:768-816      the 8x8 / 4x4 frame and field zigzag scans (ZIG(i,y,x) lists)
-
-Skipped where /root/reference is absent (the GPU box)."""
+"""
+import json
 import os
 import re
 
@@ -16,9 +17,6 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
-
-REF = "/root/reference"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present (GPU box)")
 
 ORACLE = os.path.join(ROOT, "oracle", "oracle.c")
 CSRC = os.path.join(ROOT, "x264-i386pic_amd", "csrc")
@@ -49,18 +47,19 @@ def c_array(path, name, nth=0):
     return [int(v) for v in re.findall(r"-?\d+", src[i:j + 1])]
 
 
+def _golden():
+    with open(os.path.join(ROOT, "tests", "golden", "ref_tables.json")) as fh:
+        return json.load(fh)
+
+
+def ref_array(name):
+    """Integers of the reference's constant table `name`, as recorded."""
+    return list(_golden()["arrays"][name])
+
+
 def zig_macro(name):
-    """(y, x) pairs of dct.c's ZIGZAG macro `name` in scan order (ZIG / ZIGDC(i,y,x))."""
-    src = open(os.path.join(REF, "common", "dct.c")).read()
-    m = re.search(r"#define " + name + r"\\\n((?:[^\n]*\\\n)*[^\n]*)", src)
-    assert m, name
-    items = re.findall(r"ZIG(?:DC)?\(\s*(\d+)\s*,\s*(\d+)\s*,\s*(\d+)\s*\)", m.group(1))
-    items = sorted((int(i), int(y), int(x)) for i, y, x in items)
-    assert [i for i, _, _ in items] == list(range(len(items)))
-    return [v for _, y, x in items for v in (y, x)]
-
-
-SET_C = os.path.join(REF, "common", "set.c")
+    """(y, x) pairs of dct.c's ZIGZAG macro `name` in scan order, as recorded."""
+    return list(_golden()["zigzag"][name])
 
 
 @pytest.mark.parametrize("ref_name,ours", [
@@ -72,28 +71,26 @@ SET_C = os.path.join(REF, "common", "set.c")
                      (os.path.join(CSRC, "capi.cpp"), "k_quant8_scan16")]),
 ])
 def test_cqm_scale_tables(ref_name, ours):
-    want = c_array(SET_C, ref_name)
+    want = ref_array(ref_name)
     assert len(want) in (16, 18, 36)
     for path, name in ours:
         assert c_array(path, name) == want, (path, name)
 
 
 def test_hpel_ref_tables():
-    tables = os.path.join(REF, "common", "tables.c")
     for k in (0, 1):
-        want = c_array(tables, "x264_hpel_ref%d" % k)
+        want = ref_array("x264_hpel_ref%d" % k)
         assert len(want) == 16
         assert c_array(ORACLE, "hpel_ref%d" % k) == want
         assert c_array(os.path.join(CSRC, "lookahead.hip"), "c_lr_ref%d" % k) == want
 
 
 def test_me_pattern_tables():
-    me = os.path.join(REF, "encoder", "me.c")
     la = os.path.join(CSRC, "lookahead.hip")
     for ref_name, orc_name, hip_name, n in (("mod6m1", "lr_mod6m1", "c_mod6m1", 8),
                                            ("hex2", "lr_hex2", "c_hex2", 16),
                                            ("square1", "lr_square1", "c_square1", 18)):
-        want = c_array(me, ref_name)
+        want = ref_array(ref_name)
         assert len(want) == n
         assert c_array(ORACLE, orc_name) == want, orc_name
         assert c_array(la, hip_name) == want, hip_name
@@ -131,7 +128,6 @@ def test_jvt_cqm_lists():
     """The JVT default scaling lists the checkasm CQM cases use (tests/checkasm_bufs.py,
     checkasm.c:2098-2113) equal common/tables.c:191-226."""
     import checkasm_bufs as cb
-    tables = os.path.join(REF, "common", "tables.c")
     for ours, name in ((cb.JVT4I, "x264_cqm_jvt4i"), (cb.JVT4P, "x264_cqm_jvt4p"), (cb.JVT8I, "x264_cqm_jvt8i"),
                        (cb.JVT8P, "x264_cqm_jvt8p")):
-        assert list(ours) == c_array(tables, name), name
+        assert list(ours) == ref_array(name), name

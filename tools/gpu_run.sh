@@ -4,6 +4,7 @@
 #   tests:FILES   the named test files only (comma separated, under tests/)
 #   smoke         __graft_entry__.smoke()        -> gpurun_out/TAG_smoke.log
 #   bench         default bench.py               -> gpurun_out/TAG_bench.log
+#   full          bench.py --full (side rates, roofline re-runs, cpu_baseline) -> stdout
 #   driver        bench.py --steps 20 --warmup 5 -> gpurun_out/TAG_bench_driver.log
 #   profile       tools/gpu_profile.sh (trace + FETCH / WRITE PMC of the default bench)
 #   py:SCRIPT     python tools/SCRIPT (args after '='), stdout -> gpurun_out/TAG_SCRIPT.log
@@ -31,6 +32,8 @@ for step in "$@"; do
     bench)
       timeout -k 10 400 python bench.py > gpurun_out/${TAG}_bench.log 2>&1 || { tail -20 gpurun_out/${TAG}_bench.log; exit 5; }
       tail -c 600 gpurun_out/${TAG}_bench.log; echo ;;
+    full)
+      timeout -k 10 600 python bench.py --full || exit 5 ;;
     driver)
       timeout -k 10 400 python bench.py --steps 20 --warmup 5 > gpurun_out/${TAG}_bench_driver.log 2>&1 \
         || { tail -20 gpurun_out/${TAG}_bench_driver.log; exit 5; }
