@@ -933,7 +933,7 @@ int x264hip_##BD##_me_refine_qpel_refdupe( const pixel *fenc, intptr_t fenc_stri
  * me_method X264_ME_DIA (0), X264_ME_HEX (1, x264's default, common/base.c:439),                 \
  * X264_ME_UMH (2) or X264_ME_ESA (3: the window of me.c:618-631 around the predictor stage's      \
  * winner, every candidate scored -- the decision the successive elimination of :750-768 also     \
- * reaches; nevals then counts the exhaustive form's calls; TESA stays with me_tesa): the          \
+ * reaches; nevals then counts the exhaustive form's calls; TESA: me_search_ref_tesa): the         \
  * predictor checks over mvp and the mvc list (x264_predictor_clip /                              \
  * _roundclip, common/common.h:774-805), the integer search (UMH with its adaptive range), the    \
  * qpel conversion (me.c:774-789), then refine_subpel when subme >= 2 as me_refine_subpel_ex      \
@@ -1027,6 +1027,41 @@ int x264hip_##BD##_me_search_ref_thresh( const pixel *fenc, intptr_t fenc_stride
                                          int32_t *out, int32_t *nevals,                         \
                                          int32_t *halfpel_thresh, const int32_t *ref_cost,      \
                                          const x264hip_refine_ext_t *ext, void *stream );       \
+/* x264_me_search_ref with me_method X264_ME_TESA (4; the placebo preset, common/base.c:591) for n \
+ * partitions of any size i_pixel (16x16 .. 4x4), predictors to subpel refine in one call: the   \
+ * predictor stage (me.c:214-318), the window of me.c:621-651 around its winner -- the ADS      \
+ * threshold bsad * 17 >> 4, the SAD threshold list, the halving prune and the drop-the-maximum  \
+ * prune down to me_range >> 1 entries, then COST_MV over the survivors in list order            \
+ * (me.c:653-748) -- the qpel conversion (me.c:774-789) and, at subme >= 2, refine_subpel.       \
+ * fpelcmp is SATD iff subme > 1 (mbcmp_init, encoder/encoder.c:1423-1426): COST_MV_HPEL, the     \
+ * fullpel predictor checks of subme < 3, COST_MV over the survivors and the refine's halfpel    \
+ * diamond all follow it; the scan's own SADs (bsad, me.c:659, 674, 691) stay SADs on fpel_w.    \
+ * integral8 = m->integral, the 8x8 box sums x264hip_*_frame_integral writes, at pixel (0,0) of  \
+ * frame 0, row stride ref_stride, frame stride integral_frame_stride; integral4 = the 4x4 box    \
+ * sums, frame_integral( sub8x8 = 1 )'s second plane at + stride * (lines + 64) (me.c:646-647),   \
+ * read for i_pixel > PIXEL_8x8 and required then (NULL otherwise is fine).  The kernel reads    \
+ * the integral the caller passes: x264 binds the unweighted reference's (analyse.c:1243) even    \
+ * when fpel_w is a weighted plane, and a caller that wants x264's decisions does the same.      \
+ * Every sum read lies in the rows / columns frame_integral writes as long as the window (the     \
+ * width rounded up to a multiple of 4 included) and the partition stay within the plane's        \
+ * padding less 8, which mv_limit_fpel of analyse.c:330-349 keeps.  me_range 4 .. 32.            \
+ * nevals (or NULL) = int32 [n][2]: the integer stage's fpelcmp calls (the predictor stage's plus \
+ * COST_MV over the surviving list) | get_ref calls << 16, then the refine's counts.  scan (or    \
+ * NULL) = int32 [n][2]: the scan's pixf.sad calls (the bsad call + one per ADS survivor), and    \
+ * nmvsad before the two prune loops.  Other arguments as me_search_ref_thresh (halfpel_thresh   \
+ * = NULL: the plain form). */                                                                   \
+int x264hip_##BD##_me_search_ref_tesa( const pixel *fenc, intptr_t fenc_stride,                 \
+                                       intptr_t fenc_frame_stride, const pixel *fpel_w,         \
+                                       const pixel *fpel, const pixel *hpel_h,                  \
+                                       const pixel *hpel_v, const pixel *hpel_c,                \
+                                       intptr_t ref_stride, intptr_t ref_frame_stride,          \
+                                       const uint16_t *integral8, const uint16_t *integral4,    \
+                                       intptr_t integral_frame_stride, int i_pixel, int subme,  \
+                                       int me_range, const int32_t *pos, const int16_t *par,    \
+                                       const int16_t *mvc, const uint16_t *cost_mv, int n,      \
+                                       int32_t *out, int32_t *nevals, int32_t *scan,            \
+                                       int32_t *halfpel_thresh, const int32_t *ref_cost,        \
+                                       const x264hip_refine_ext_t *ext, void *stream );         \
                                                                                                 \
 /* block lists of the reference transforms (dct.c), device arrays;                             \
  * dct holds n consecutive outputs of the selected entry's size. */                             \

@@ -29,6 +29,7 @@ __all__ = [
     "PIXEL_8x8", "PIXEL_8x4", "PIXEL_4x8", "PIXEL_4x4", "PIXEL_4x16", "PIXEL_SIZES",
     "CMP_SAD", "CMP_SSD", "CMP_SATD", "CPU_HIP", "set_variant", "set_thread_device", "thread_device",
     "backend_banner", "forward_ref", "upload", "me_bind", "MeBinding", "weight_scale_plane", "stream_pair", "stream_pair_destroy", "me_search_full8",
+    "me_search_ref_tesa", "me_refine_bidir", "me_refine_qpel_refdupe", "plane_upload", "upload_plane", "upload_planes",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -1342,6 +1343,41 @@ def me_search_ref(fenc, fenc_origin, fenc_stride, fpel_w, planes, ref_origin, re
            ref_stride, rfs, i_pixel, me_method, subme, me_range, _ptr(pos), _ptr(par), _ptr(mvc), _ptr(cm, c0), n,
            _ptr(out), _ptr(nevals) if nevals is not None else None, *extra,
            _c.byref(ext) if ext is not None else None, _stream()), name)
+    return out
+
+
+def me_search_ref_tesa(fenc, fenc_origin, fenc_stride, fpel_w, planes, ref_origin, ref_stride, integral, i_pixel, subme,
+                       me_range, pos, par, mvc, cost_mv_center, out=None, fenc_frame_stride=None, ref_frame_stride=None,
+                       nevals=None, scan=None, ext=None, halfpel_thresh=None, ref_cost=None, integral_origin=None):
+    """x264_me_search_ref with X264_ME_TESA of n partitions of any size (x264hip_*_me_search_ref_tesa;
+    encoder/me.c:214-318, 618-749, 774-797), fpelcmp = SATD iff subme > 1.  integral:
+    frame_integral(..., sub8x8=True)'s tensor [n, 2 * (lines + 2 * PAD), ref_stride] of the
+    unweighted reference (its (0,0) at integral_origin, default PAD * stride + PAD; the 4x4 plane
+    is its second half); a single-plane integral (sub8x8=False) serves i_pixel <= PIXEL_8x8.
+    me_range 4 .. 32.  Other arguments and the result as me_search_ref; scan: optional int32
+    [n, 2] (the scan's SAD calls, nmvsad before the prunes)."""
+    import torch
+    bd = _pix_bd(fenc)
+    n = pos.shape[0]
+    if out is None:
+        out = torch.empty((n, 4), dtype=torch.int32, device=fenc.device)
+    ffs = fenc_frame_stride if fenc_frame_stride is not None else (fenc[0].numel() if fenc.dim() == 3 else 0)
+    rfs = ref_frame_stride if ref_frame_stride is not None else _frame_stride(fpel_w, *planes)
+    io = integral_origin if integral_origin is not None else PAD * ref_stride + PAD
+    # frame_integral(sub8x8=True): twice the reference plane's rows, the 4x4 sums in the second half
+    rows = integral.shape[-2]
+    i4 = _ptr(integral, io + (rows // 2) * ref_stride) if rows == 2 * planes[0].shape[-2] else None
+    cm, c0 = cost_mv_center
+    name = f"x264hip_{bd}_me_search_ref_tesa"
+    fn = getattr(lib(), name)
+    fn.argtypes = [_P, _IP, _IP, _P, _P, _P, _P, _P, _IP, _IP, _P, _P, _IP, _c.c_int, _c.c_int, _c.c_int, _P, _P, _P,
+                   _P, _c.c_int, _P, _P, _P, _P, _P, _P, _P]
+    fn.restype = _c.c_int
+    opt = lambda t: _ptr(t) if t is not None else None
+    _rc(fn(_ptr(fenc, fenc_origin), fenc_stride, ffs, _ptr(fpel_w, ref_origin), *[_ptr(p, ref_origin) for p in planes],
+           ref_stride, rfs, _ptr(integral, io), i4, integral[0].numel() if integral.dim() == 3 else 0, i_pixel, subme,
+           me_range, _ptr(pos), _ptr(par), _ptr(mvc), _ptr(cm, c0), n, _ptr(out), opt(nevals), opt(scan),
+           opt(halfpel_thresh), opt(ref_cost), _c.byref(ext) if ext is not None else None, _stream()), name)
     return out
 
 

@@ -2013,6 +2013,25 @@ extern "C" const char *x264hip_backend_banner( void )
                                                   me_range, pos, par, mvc, cost_mv, n, out, nevals, halfpel_thresh,  \
                                                   ref_cost, ext, (hipStream_t)stream ), "me_search_ref_thresh" );    \
     }                                                                                                                \
+    extern "C" int x264hip_##BD##_me_search_ref_tesa(                                                             \
+        const PT<BD>::pixel *fenc, intptr_t fs, intptr_t ffs, const PT<BD>::pixel *fw, const PT<BD>::pixel *p0,       \
+        const PT<BD>::pixel *p1, const PT<BD>::pixel *p2, const PT<BD>::pixel *p3, intptr_t rs, intptr_t rfs,         \
+        const uint16_t *integral8, const uint16_t *integral4, intptr_t ifs, int i_pixel, int subme, int me_range,    \
+        const int32_t *pos, const int16_t *par, const int16_t *mvc, const uint16_t *cost_mv, int n, int32_t *out,    \
+        int32_t *nevals, int32_t *scan, int32_t *halfpel_thresh, const int32_t *ref_cost,                            \
+        const x264hip_refine_ext_t *ext, void *stream )                                                              \
+    {                                                                                                                \
+        if( n < 0 || i_pixel < 0 || i_pixel > 6 || subme < 1 || subme > 11 || me_range < 4 || me_range > 32 ||       \
+            ( (uintptr_t)out & 15 ) || ( i_pixel > 3 && !integral4 ) ||                                              \
+            ( n > 0 && ( !fenc || !fw || !p0 || !p1 || !p2 || !p3 || !integral8 || !pos || !par || !mvc ||           \
+                         !cost_mv || !out ) ) )                                                                      \
+            return X264HIP_EINVAL;                                                                                   \
+        const PT<BD>::pixel *planes[4] = { p0, p1, p2, p3 };                                                         \
+        return map_err( launch_me_search_ref_tesa<BD>( fenc, fs, ffs, fw, planes, rs, rfs, integral8, integral4,     \
+                                                       ifs, i_pixel, subme, me_range, pos, par, mvc, cost_mv, n,     \
+                                                       out, nevals, scan, halfpel_thresh, ref_cost, ext,             \
+                                                       (hipStream_t)stream ), "me_search_ref_tesa" );                \
+    }                                                                                                                \
     extern "C" int x264hip_##BD##_sub_dct_batch( int kind, const PT<BD>::pixel *fenc, intptr_t fs,                  \
                                                  const PT<BD>::pixel *fdec, intptr_t ds, const int64_t *fo,          \
                                                  const int64_t *dofs, int n, PT<BD>::dctcoef *dct, void *stream )    \

@@ -435,6 +435,30 @@ hipError_t launch_me_search_ref( const typename PT<BD>::pixel *fenc, intptr_t fs
                                  const int32_t *pos, const int16_t *par, const int16_t *mvc, const uint16_t *cost_mv,
                                  int n, int32_t *out, int32_t *nevals, int32_t *thr, const int32_t *rcost,
                                  const x264hip_refine_ext_t *ext, hipStream_t stream );
+// TESA through x264_me_search_ref (x264hip_*_me_search_ref_tesa): the predictor stage with
+// fpelcmp = SATD at subme > 1 and the refine of an integer stage's rpar / rinit (refine.hip), the
+// window stage and the whole call (search_tesa.hip).  stage: int32 [n][8], 16-byte aligned
+template <int BD>
+hipError_t launch_me_search_pred( const typename PT<BD>::pixel *fenc, intptr_t fs, intptr_t ffs,
+                                  const typename PT<BD>::pixel *fw, const typename PT<BD>::pixel *const planes[4],
+                                  intptr_t rs, intptr_t rfs, int i_pixel, int subme, const int32_t *pos,
+                                  const int16_t *par, const int16_t *mvc, const uint16_t *cost_mv, int n,
+                                  int32_t *stage, const x264hip_refine_ext_t *ext, hipStream_t stream );
+template <int BD>
+hipError_t launch_me_search_refine( const typename PT<BD>::pixel *fenc, intptr_t fs, intptr_t ffs,
+                                    const typename PT<BD>::pixel *const planes[4], intptr_t rs, intptr_t rfs,
+                                    int i_pixel, int subme, int fpel_satd, const int32_t *pos, const int16_t *rpar,
+                                    const int32_t *rinit, const uint16_t *cost_mv, int n, int32_t *out,
+                                    int32_t *nevals, int32_t *thr, const int32_t *rcost,
+                                    const x264hip_refine_ext_t *ext, hipStream_t stream );
+template <int BD>
+hipError_t launch_me_search_ref_tesa( const typename PT<BD>::pixel *fenc, intptr_t fs, intptr_t ffs,
+                                      const typename PT<BD>::pixel *fw, const typename PT<BD>::pixel *const planes[4],
+                                      intptr_t rs, intptr_t rfs, const uint16_t *integral8, const uint16_t *integral4,
+                                      intptr_t ifs, int i_pixel, int subme, int me_range, const int32_t *pos,
+                                      const int16_t *par, const int16_t *mvc, const uint16_t *cost_mv, int n,
+                                      int32_t *out, int32_t *nevals, int32_t *scan, int32_t *thr,
+                                      const int32_t *rcost, const x264hip_refine_ext_t *ext, hipStream_t stream );
 // x264's P16x16 reference-0 analysis with mvpred.c's predictors, as an MB wavefront (refine.hip)
 template <int BD>
 hipError_t launch_me_analyse_p16x16( const typename PT<BD>::pixel *fenc, intptr_t fs, intptr_t ffs,

@@ -971,7 +971,11 @@ __device__ __forceinline__ void sad4_tile( const uint32_t (&fa)[4][8 / PT<BD>::P
     }
 }
 
-template <int BD, int IPIX, bool WGT, bool ESA>
+// PRED: the predictor stage alone (me.c:214-318) with fpelcmp switchable to SATD (TESA with
+// subme > 1, encoder.c:1423-1426: COST_MV_HPEL, the fullpel checks of subme < 3 and COST_MV), its
+// state stored for the TESA window kernel (search_tesa.hip) through `out`, here int32 [n][8] =
+// { bmx | bmy << 16, bcost, bpred_cost, bpred_mv, pmv, fpelcmp calls | get_ref calls << 16, 0, 0 }
+template <int BD, int IPIX, bool WGT, bool ESA, bool PRED>
 __global__ __launch_bounds__( 256 ) void me_search_ref_kernel(
     const typename PT<BD>::pixel *__restrict__ fenc, intptr_t fs, intptr_t ffs, const typename PT<BD>::pixel *fw,
     const typename PT<BD>::pixel *p0, const typename PT<BD>::pixel *p1, const typename PT<BD>::pixel *p2,
@@ -1008,6 +1012,13 @@ __global__ __launch_bounds__( 256 ) void me_search_ref_kernel(
     const uint16_t *cmx = cost_mv - mvpx, *cmy = cost_mv - mvpy;
     int nf = 0, nh = 0;                                   // the reference's fpelcmp / get_ref calls
 
+    // fpelcmp = SATD: only TESA's predictor stage at subme > 1 (a constant false otherwise)
+    auto fsatd = [&]() __attribute__( ( always_inline ) ) {
+        if constexpr( PRED )
+            return subme > 1;
+        else
+            return false;
+    };
     // mode 0: fpelcmp on p_fref_w + BITS_MVD; 1: COST_MV_HPEL (get_ref + qpel mv cost); 2: fpelcmp
     // alone.  Group g scores (gx, gy) (not read when !ok); c[k] = group k's cost.
     auto evalc = [&]( int gx, int gy, int mode, bool ok, int (&c)[4] ) __attribute__( ( always_inline ) ) {
@@ -1016,13 +1027,15 @@ __global__ __launch_bounds__( 256 ) void me_search_ref_kernel(
         {
             if( mode == 1 )
             {
-                v = tile_cost<BD, false, WGT, TW>( fa, q0, q1, q2, q3, rs, gx, gy, wt0 );
+                v = fsatd() ? tile_cost<BD, true, WGT, TW>( fa, q0, q1, q2, q3, rs, gx, gy, wt0 ) >> 1
+                            : tile_cost<BD, false, WGT, TW>( fa, q0, q1, q2, q3, rs, gx, gy, wt0 );
                 if( u == 0 )
                     v += (uint32_t)cmx[gx] + (uint32_t)cmy[gy];
             }
             else
             {
-                v = tile_cost<BD, false, false, TW>( fa, qw, qw, qw, qw, rs, 4 * gx, 4 * gy );
+                v = fsatd() ? tile_cost<BD, true, false, TW>( fa, qw, qw, qw, qw, rs, 4 * gx, 4 * gy ) >> 1
+                            : tile_cost<BD, false, false, TW>( fa, qw, qw, qw, qw, rs, 4 * gx, 4 * gy );
                 if( u == 0 && mode == 0 )
                     v += (uint32_t)cmx[4 * gx] + (uint32_t)cmy[4 * gy];
             }
@@ -1177,6 +1190,15 @@ __global__ __launch_bounds__( 256 ) void me_search_ref_kernel(
         }
     }
 
+    if constexpr( PRED )
+    {
+        if( live && lane == sbase )
+        {
+            *(int4 *)(out + 8 * j) = make_int4( (int)sr_pack( bmx, bmy ), bcost, bpred_cost, (int)bpred_mv );
+            *(int4 *)(out + 8 * j + 4) = make_int4( (int)pmv, nf | (nh << 16), 0, 0 );
+        }
+        return;
+    }
     // the diamond of radius 1 around (cx, cy) in COST_MV_X4's order (0,-1) (0,1) (-1,0) (1,0)
     auto dia = [&]( int cx, int cy ) __attribute__( ( always_inline ) ) {
         evalc( cx + (g == 2 ? -1 : g == 3 ? 1 : 0), cy + (g == 0 ? -1 : g == 1 ? 1 : 0), 0, true, c );
@@ -1522,6 +1544,74 @@ __global__ __launch_bounds__( 256 ) void me_search_ref_kernel(
     }
 }
 
+// TESA's predictor stage (me_search_ref_kernel's PRED form), then the window kernel of search_tesa.hip
+template <int BD>
+hipError_t launch_me_search_pred( const typename PT<BD>::pixel *fenc, intptr_t fs, intptr_t ffs,
+                                  const typename PT<BD>::pixel *fw, const typename PT<BD>::pixel *const planes[4],
+                                  intptr_t rs, intptr_t rfs, int i_pixel, int subme, const int32_t *pos,
+                                  const int16_t *par, const int16_t *mvc, const uint16_t *cost_mv, int n,
+                                  int32_t *stage, const x264hip_refine_ext_t *xe, hipStream_t stream )
+{
+    if( n <= 0 )
+        return hipSuccess;
+    if( i_pixel < 0 || i_pixel > 6 || subme < 1 || subme > 11 || ((uintptr_t)stage & 15) )
+        return hipErrorInvalidValue;
+    RsExt<BD> ext;
+    int mode;
+    if( rs_ext<BD>( xe, ext, mode ) != hipSuccess )
+        return hipErrorInvalidValue;
+    const int64_t lanes = (int64_t)n * 4 * part_tiles( i_pixel );
+    dim3 blk( 256 ), g( (unsigned)((lanes + 255) / 256) );
+#define SP_GO( I, W )                                                                                             \
+    hipLaunchKernelGGL( ( me_search_ref_kernel<BD, I, W, false, true> ), g, blk, 0, stream, fenc, fs, ffs, fw,    \
+                        planes[0], planes[1], planes[2], planes[3], rs, rfs, n, 4, subme, 0, pos, par, mvc,       \
+                        cost_mv, ext.wt[0], stage, nullptr, nullptr, nullptr )
+#define SP_CASE( I )                                                                                              \
+    case I:                                                                                                       \
+        if( ext.wt[0].on ) { SP_GO( I, true ); } else { SP_GO( I, false ); }                                      \
+        break;
+    switch( i_pixel )
+    {
+        SP_CASE( 0 ) SP_CASE( 1 ) SP_CASE( 2 ) SP_CASE( 3 ) SP_CASE( 4 ) SP_CASE( 5 ) SP_CASE( 6 )
+        default: break;
+    }
+#undef SP_CASE
+#undef SP_GO
+    return hipGetLastError();
+}
+template hipError_t launch_me_search_pred<8>( const uint8_t *, intptr_t, intptr_t, const uint8_t *,
+                                              const uint8_t *const[4], intptr_t, intptr_t, int, int, const int32_t *,
+                                              const int16_t *, const int16_t *, const uint16_t *, int, int32_t *,
+                                              const x264hip_refine_ext_t *, hipStream_t );
+template hipError_t launch_me_search_pred<10>( const uint16_t *, intptr_t, intptr_t, const uint16_t *,
+                                               const uint16_t *const[4], intptr_t, intptr_t, int, int,
+                                               const int32_t *, const int16_t *, const int16_t *, const uint16_t *,
+                                               int, int32_t *, const x264hip_refine_ext_t *, hipStream_t );
+
+// x264_me_search_ref's refine after an integer stage that left rpar / rinit (me.c:791-797): nevals
+// (or NULL) points at the partition's second count, two int32 per partition
+template <int BD>
+hipError_t launch_me_search_refine( const typename PT<BD>::pixel *fenc, intptr_t fs, intptr_t ffs,
+                                    const typename PT<BD>::pixel *const planes[4], intptr_t rs, intptr_t rfs,
+                                    int i_pixel, int subme, int fpel_satd, const int32_t *pos, const int16_t *rpar,
+                                    const int32_t *rinit, const uint16_t *cost_mv, int n, int32_t *out,
+                                    int32_t *nevals, int32_t *thr, const int32_t *rcost,
+                                    const x264hip_refine_ext_t *xe, hipStream_t stream )
+{
+    return refine_launch<BD>( fenc, fs, ffs, planes, rs, rfs, i_pixel, subme, 0, fpel_satd, pos, rpar, rinit, cost_mv,
+                              n, out, nevals, 2, thr, rcost, xe, stream );
+}
+template hipError_t launch_me_search_refine<8>( const uint8_t *, intptr_t, intptr_t, const uint8_t *const[4], intptr_t,
+                                                intptr_t, int, int, int, const int32_t *, const int16_t *,
+                                                const int32_t *, const uint16_t *, int, int32_t *, int32_t *,
+                                                int32_t *, const int32_t *, const x264hip_refine_ext_t *,
+                                                hipStream_t );
+template hipError_t launch_me_search_refine<10>( const uint16_t *, intptr_t, intptr_t, const uint16_t *const[4],
+                                                 intptr_t, intptr_t, int, int, int, const int32_t *, const int16_t *,
+                                                 const int32_t *, const uint16_t *, int, int32_t *, int32_t *,
+                                                 int32_t *, const int32_t *, const x264hip_refine_ext_t *,
+                                                 hipStream_t );
+
 template <int BD>
 hipError_t launch_me_search_ref( const typename PT<BD>::pixel *fenc, intptr_t fs, intptr_t ffs,
                                  const typename PT<BD>::pixel *fw, const typename PT<BD>::pixel *const planes[4],
@@ -1555,13 +1645,13 @@ hipError_t launch_me_search_ref( const typename PT<BD>::pixel *fenc, intptr_t fs
     dim3 blk( 256 ), g( (unsigned)((lanes + 255) / 256) );
 #define SR_GO( I, W )                                                                                             \
     if( me_method == 3 )                                                                                          \
-        hipLaunchKernelGGL( ( me_search_ref_kernel<BD, I, W, true> ), g, blk, 0, stream, fenc, fs, ffs, fw,       \
-                            planes[0], planes[1], planes[2], planes[3], rs, rfs, n, me_method, subme, me_range,   \
-                            pos, par, mvc, cost_mv, ext.wt[0], out, rpar, rinit, nevals );                        \
+        hipLaunchKernelGGL( ( me_search_ref_kernel<BD, I, W, true, false> ), g, blk, 0, stream, fenc, fs, ffs,    \
+                            fw, planes[0], planes[1], planes[2], planes[3], rs, rfs, n, me_method, subme,         \
+                            me_range, pos, par, mvc, cost_mv, ext.wt[0], out, rpar, rinit, nevals );              \
     else                                                                                                          \
-    hipLaunchKernelGGL( ( me_search_ref_kernel<BD, I, W, false> ), g, blk, 0, stream, fenc, fs, ffs, fw, planes[0], \
-                        planes[1], planes[2], planes[3], rs, rfs, n, me_method, subme, me_range, pos, par, mvc,     \
-                        cost_mv, ext.wt[0], out, rpar, rinit, nevals )
+        hipLaunchKernelGGL( ( me_search_ref_kernel<BD, I, W, false, false> ), g, blk, 0, stream, fenc, fs, ffs,   \
+                            fw, planes[0], planes[1], planes[2], planes[3], rs, rfs, n, me_method, subme,         \
+                            me_range, pos, par, mvc, cost_mv, ext.wt[0], out, rpar, rinit, nevals )
 #define SR_CASE( I )                                                                                              \
     case I:                                                                                                       \
         if( ext.wt[0].on ) { SR_GO( I, true ); } else { SR_GO( I, false ); }                                      \
