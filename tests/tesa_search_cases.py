@@ -16,6 +16,7 @@ import numpy as np
 import numpy_ref as nr
 import refine_cases as rc
 import search_cases as sc
+from degenerate_cases import flat_case  # noqa: F401  (the near-flat case lives with the other degenerate content)
 from test_cpu_refine_chroma import _weigh
 
 PAD = 32
@@ -283,17 +284,6 @@ def refine_fpel_satd_py(*args, **kw):
 
 
 # ---------------------------------------------------------------- inputs
-def flat_case(bd, W, H, cf, seed):
-    """a ChromaCase whose luma is near flat (the texture's top three bits around a mid level): with
-    a high-lambda mv cost the rows' ycost reaches bsad (the row skip) and survivor lists empty"""
-    cc = rc.ChromaCase(bd, W, H, cf, seed=seed)
-    for fr in (cc.ref, cc.fenc):
-        fr.y = ((fr.y.astype(np.int64) >> (bd - 3)) + (100 << (bd - 8))).astype(fr.y.dtype)
-    cc.luma = [cc.ref.y.ravel()] + [h.ravel() for h in nr.hpel_planes(cc.ref.y, PAD, W, H, bd)]
-    cc.fenc_y = cc.fenc.y.ravel()
-    return cc
-
-
 def degenerate_jobs(mbw, mbh, i_pixel, seed):
     """search_cases.jobs with every third partition's x limits equal (a window of width 0) and
     every fifth's y limits equal (one row), at the predictor's rounded position"""

@@ -20,9 +20,11 @@ def _t(a, bd):
 
 
 def _run(hip, oracle, bd, W, H, nframes, me_method, subme, me_range, chroma, seed, mv_range=512, lowres=False,
-         temporal=False):
+         temporal=False, cases=None, cost=None, tag=()):
+    """cases / cost: the frame pairs and the mv cost (table, index of mvd 0) in place of the seeded
+    ones; tag: what a failing message names the inputs by"""
     cf = 1
-    cases = [rc.ChromaCase(bd, W, H, cf, seed=seed + 11 * k) for k in range(nframes)]
+    cases = cases or [rc.ChromaCase(bd, W, H, cf, seed=seed + 11 * k) for k in range(nframes)]
     c0_ = cases[0]
     rows = c0_.ref.y.shape[0]
     crows = c0_.ref.nv.shape[0]
@@ -40,7 +42,7 @@ def _run(hip, oracle, bd, W, H, nframes, me_method, subme, me_range, chroma, see
     if temporal:
         tm = rs.integers(-90, 90, (nframes, nmb, 2)).astype(np.int16)
     tscale = 384 if temporal else 0
-    cm, c0 = rc.cost_mv()
+    cm, c0 = cost or rc.cost_mv()
     cmd = torch.from_numpy(cm.view(np.int16)).cuda()
     ext = hip.refine_ext(chroma, cf, 0, (None, None, None), fenc_chroma=fenc_c, fenc_chroma_origin=c0_.co,
                          fenc_chroma_stride=c0_.cs, ref_chroma=ref_c, ref_chroma_origin=c0_.co,
@@ -63,9 +65,9 @@ def _run(hip, oracle, bd, W, H, nframes, me_method, subme, me_range, chroma, see
         want, wne = mp.analyse_p16x16(search, mbw, mbh, mv_range, None if lr is None else lr[f],
                                       None if tm is None else tm[f], tscale)
         bad = np.argwhere((got[f] != want).any(1)).ravel()
-        assert not len(bad), (f, bad[:4], got[f][bad[:4]], want[bad[:4]])
+        assert not len(bad), (*tag, f, bad[:4], got[f][bad[:4]], want[bad[:4]])
         badn = np.argwhere((ne[f] != wne).any(1)).ravel()
-        assert not len(badn), (f, badn[:4], ne[f][badn[:4]], wne[badn[:4]])
+        assert not len(badn), (*tag, f, badn[:4], ne[f][badn[:4]], wne[badn[:4]])
     return got
 
 

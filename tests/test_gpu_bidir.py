@@ -19,14 +19,16 @@ def _t(a, bd):
     return torch.from_numpy(a.view(np.int16) if bd == 10 else a).cuda()
 
 
-def _run(hip, oracle, bd, W, H, i_pixel, satd, seed, weights=(32, 24, 44, 32, -8)):
-    mr = sc.MultiRef(bd, W, H, 1, seed=seed)
+def _run(hip, oracle, bd, W, H, i_pixel, satd, seed, weights=(32, 24, 44, 32, -8), mr=None, cost=None, tag=()):
+    """mr / cost: the MultiRef and the mv cost (table, index of mvd 0) in place of the seeded ones;
+    tag: what a failing message names the inputs by"""
+    mr = mr or sc.MultiRef(bd, W, H, 1, seed=seed)
     rows = mr.fenc_y.size // mr.stride
     fenc = _t(mr.fenc_y.reshape(1, rows, -1), bd)
     l0 = [_t(p.reshape(1, rows, -1), bd) for p in mr.refs[0].luma]
     l1 = [_t(p.reshape(1, rows, -1), bd) for p in mr.refs[1].luma]
     pos, par, wt = bc.jobs(mr, i_pixel, seed=seed + 3, weights=weights)
-    cm, c0 = rc.cost_mv()
+    cm, c0 = cost or rc.cost_mv()
     cmd = torch.from_numpy(cm.view(np.int16)).cuda()
     n = len(pos)
     cost = torch.full((n,), -1, dtype=torch.int32, device="cuda")
@@ -37,9 +39,11 @@ def _run(hip, oracle, bd, W, H, i_pixel, satd, seed, weights=(32, 24, 44, 32, -8
     want, wcost, wne = oracle.me_refine_bidir(bd, mr.fenc_y, mr.origin, mr.stride, mr.refs[0].luma, mr.refs[1].luma,
                                               mr.origin, mr.stride, i_pixel, satd, pos[:, 1:], par, wt, cm, c0)
     bad = np.argwhere((got != want).any(1)).ravel()
-    assert not len(bad), (bad[:4], got[bad[:4]], want[bad[:4]])
-    assert np.array_equal(cost.cpu().numpy(), wcost)
-    assert np.array_equal(ne.cpu().numpy(), wne)
+    assert not len(bad), (*tag, bad[:4], got[bad[:4]], want[bad[:4]])
+    badc = np.argwhere(cost.cpu().numpy() != wcost).ravel()
+    assert not len(badc), (*tag, badc[:4], cost.cpu().numpy()[badc[:4]], wcost[badc[:4]])
+    badn = np.argwhere(ne.cpu().numpy() != wne).ravel()
+    assert not len(badn), (*tag, badn[:4], ne.cpu().numpy()[badn[:4]], wne[badn[:4]])
     return want, wne
 
 

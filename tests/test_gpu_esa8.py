@@ -13,12 +13,14 @@ import esa8_cases as ec
 pytestmark = pytest.mark.gpu
 
 
-def _run(hip, oracle, bd, W, H, nf, R, me_range, seed, **kw):
+def _run(hip, oracle, bd, W, H, nf, R, me_range, seed, frames=None, cost=None, tag=(), **kw):
+    """frames / cost: (planes, stride, origin) and the mv cost (table, index of mvd 0) in place of
+    the seeded ones; tag: what a failing message names the inputs by"""
     from x264hip import synth
-    planes, stride, origin = synth.make_sequence(nf + 1, W, H, bd, seed=seed)
+    planes, stride, origin = frames or synth.make_sequence(nf + 1, W, H, bd, seed=seed)
     mbw, mbh = W // 16, H // 16
     nmb = mbw * mbh
-    cm, c0 = ec.cost_mv()
+    cm, c0 = cost or ec.cost_mv()
     cen, par, ic = [], [], []
     for f in range(nf):
         c, p, i = ec.jobs(mbw, mbh, me_range, seed=seed * 10 + f, **kw)
@@ -36,7 +38,7 @@ def _run(hip, oracle, bd, W, H, nf, R, me_range, seed, **kw):
         want = oracle.me_search_esa8(bd, planes[f + 1].ravel(), origin, stride, planes[f].ravel(), origin, stride,
                                      mbw, mbh, me_range, par[sl], ic[sl], cm, c0)
         bad = np.argwhere((got[sl] != want).any(1)).ravel()
-        assert len(bad) == 0, f"frame {f}: partitions {bad[:8]} got {got[sl][bad[:4]]} want {want[bad[:4]]}"
+        assert len(bad) == 0, f"{tag} frame {f}: partitions {bad[:8]} got {got[sl][bad[:4]]} want {want[bad[:4]]}"
     return got, par, ic
 
 

@@ -27,10 +27,12 @@ def _unequal(lows):
 
 
 def _case(hip, oracle, bd, W, H, npairs, me_method, subme, satd, random=False, aq=False, me_range=16, n_slices=1,
-          unequal=False):
+          unequal=False, frames=None, tag=()):
+    """frames: (planes [npairs + 1, ...], stride, origin) in place of the generated sequence; tag:
+    what a failing message names the inputs by"""
     from x264hip import synth
     gen = synth.random_planes if random else synth.make_sequence
-    frames, stride, origin = gen(npairs + 1, W, H, bd)
+    frames, stride, origin = frames or gen(npairs + 1, W, H, bd)
     dev = torch.from_numpy(frames.view(np.int16) if bd == 10 else frames).cuda()
     lows, ls = hip.frame_init_lowres(dev, origin, stride, W, H)
     mbw, mbh = W // 16, H // 16
@@ -58,7 +60,8 @@ def _case(hip, oracle, bd, W, H, npairs, me_method, subme, satd, random=False, a
         names = ("mvs", "mv_costs", "lowres_costs", "row_satd", "est")
         for name, g, w in zip(names, got, want):
             g = g[f].reshape(w.shape).view(w.dtype) if name == "lowres_costs" else g[f].reshape(w.shape)
-            assert np.array_equal(g, w), (f, name, np.argwhere(g != w)[:4])
+            bad = np.argwhere(g != w)[:4]
+            assert not len(bad), (*tag, f, name, bad, g[tuple(bad.T)], w[tuple(bad.T)])
     return got
 
 
@@ -127,12 +130,13 @@ def test_lowres_inter_identical(hip, oracle):
 
 
 def _bidir_case(hip, oracle, bd, W, H, n, search, me_method, subme, satd, dsf, weight, with_p1=True, random=False,
-                aq=False, me_range=16, n_slices=1, unequal=False):
+                aq=False, me_range=16, n_slices=1, unequal=False, frames=None, tag=()):
     """n B triplets (p0, b, p1) = (3i, 3i+1, 3i+2) of one sequence; the list searches (or the
-    cached mvs of a first pass) and every output against the oracle."""
+    cached mvs of a first pass) and every output against the oracle.  frames: (planes [3 n, ...],
+    stride, origin) in place of the generated sequence"""
     from x264hip import synth
     gen = synth.random_planes if random else synth.make_sequence
-    frames, stride, origin = gen(3 * n, W, H, bd)
+    frames, stride, origin = frames or gen(3 * n, W, H, bd)
     dev = torch.from_numpy(frames.view(np.int16) if bd == 10 else frames).cuda()
     lows, ls = hip.frame_init_lowres(dev, origin, stride, W, H)
     mbw, mbh = W // 16, H // 16
@@ -179,7 +183,8 @@ def _bidir_case(hip, oracle, bd, W, H, n, search, me_method, subme, satd, dsf, w
         order = (0, 2, 1, 3, 4, 5, 6)            # oracle returns m0, k0, m1, k1, lc, rows, est
         for name, k, w in zip(("mvs0", "costs0", "mvs1", "costs1", "lowres_costs", "row_satd", "est"), order, want):
             g = got[k][i].reshape(w.shape)
-            assert np.array_equal(g, w), (i, name, np.argwhere(g != w)[:4])
+            bad = np.argwhere(g != w)[:4]
+            assert not len(bad), (*tag, i, name, bad, g[tuple(bad.T)], w[tuple(bad.T)])
 
 
 @pytest.mark.parametrize("bd", [8, 10])

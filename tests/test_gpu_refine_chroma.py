@@ -21,8 +21,10 @@ def _t(a, bd):
 
 
 def _run(hip, oracle, bd, cf, W, H, nframes, i_pixel, subme, refine_qpel, b_chroma_me, weights, fpel_satd=0,
-         seed=1, cost_scale=1):
-    cases = [rc.ChromaCase(bd, W, H, cf, seed=seed + 17 * k, fade=any(w is not None for w in weights))
+         seed=1, cost_scale=1, cases=None, cost=None, tag=()):
+    """cases / cost: the frame pairs and the mv cost (table, index of mvd 0) in place of the seeded
+    ones; tag: what a failing message names the inputs by"""
+    cases = cases or [rc.ChromaCase(bd, W, H, cf, seed=seed + 17 * k, fade=any(w is not None for w in weights))
              for k in range(nframes)]
     c0_ = cases[0]
     rows = c0_.ref.y.shape[0]
@@ -32,8 +34,8 @@ def _run(hip, oracle, bd, cf, W, H, nframes, i_pixel, subme, refine_qpel, b_chro
     fenc_c = [_t(np.stack([c.fenc_c[k].reshape(crows, -1) for c in cases]), bd) for k in range(len(c0_.fenc_c))]
     ref_c = [_t(np.stack([c.ref_c[k].reshape(crows, -1) for c in cases]), bd) for k in range(len(c0_.ref_c))]
     mbw, mbh = W // 16, H // 16
+    cm, c0 = cost or rc.cost_mv()
     pos, par, cost = rc.jobs(mbw, mbh, nframes, i_pixel, seed + subme, cost_scale=(1 << (bd - 8)) * cost_scale)
-    cm, c0 = rc.cost_mv()
     cmd = torch.from_numpy(cm.view(np.int16)).cuda()
     ext = hip.refine_ext(b_chroma_me, cf, 0, weights, fenc_chroma=fenc_c, fenc_chroma_origin=c0_.co,
                          fenc_chroma_stride=c0_.cs, ref_chroma=ref_c, ref_chroma_origin=c0_.co,
@@ -52,9 +54,9 @@ def _run(hip, oracle, bd, cf, W, H, nframes, i_pixel, subme, refine_qpel, b_chro
                                             counts=True, ext=oext, fenc_c=c.fenc_c, fc_origin=c.co, fcs=c.cs,
                                             ref_c=c.ref_c, rc_origin=c.co, rcs=c.cs)
         bad = np.argwhere((got[sel] != want).any(1)).ravel()
-        assert not len(bad), (f, bad[:4], got[sel][bad[:4]], want[bad[:4]])
+        assert not len(bad), (*tag, f, bad[:4], got[sel][bad[:4]], want[bad[:4]])
         badn = np.argwhere(ne[sel] != wne).ravel()
-        assert not len(badn), (f, badn[:4], [hex(v) for v in ne[sel][badn[:4]]], [hex(v) for v in wne[badn[:4]]])
+        assert not len(badn), (*tag, f, badn[:4], [hex(v) for v in ne[sel][badn[:4]]], [hex(v) for v in wne[badn[:4]]])
     return got, par, ne
 
 

@@ -20,9 +20,12 @@ def _t(a, bd):
     return torch.from_numpy(a.view(np.int16) if bd == 10 else a).cuda()
 
 
-def _run(hip, oracle, bd, cf, W, H, nframes, i_pixel, me_method, subme, me_range, fade, chroma, seed):
+def _run(hip, oracle, bd, cf, W, H, nframes, i_pixel, me_method, subme, me_range, fade, chroma, seed, cases=None,
+         jobs=None, cost=None, tag=()):
+    """cases / jobs / cost: the frame pairs, (pos, par, mvc) and (table, index of mvd 0) in place of
+    the seeded ones; tag: what a failing message names the inputs by"""
     weights = rc.FADE_WEIGHTS if fade else (None, None, None)
-    cases = [rc.ChromaCase(bd, W, H, cf, seed=seed + 11 * k, fade=fade) for k in range(nframes)]
+    cases = cases or [rc.ChromaCase(bd, W, H, cf, seed=seed + 11 * k, fade=fade) for k in range(nframes)]
     c0_ = cases[0]
     rows = c0_.ref.y.shape[0]
     crows = (c0_.ref.nv if cf in (1, 2) else c0_.ref.u).shape[0]
@@ -33,8 +36,8 @@ def _run(hip, oracle, bd, cf, W, H, nframes, i_pixel, me_method, subme, me_range
     fw = _t(np.stack([w.reshape(rows, -1) for w in fws]), bd)
     fenc_c = [_t(np.stack([c.fenc_c[k].reshape(crows, -1) for c in cases]), bd) for k in range(len(c0_.fenc_c))]
     ref_c = [_t(np.stack([c.ref_c[k].reshape(crows, -1) for c in cases]), bd) for k in range(len(c0_.ref_c))]
-    pos, par, mvc = sc.jobs(W // 16, H // 16, nframes, i_pixel, seed=seed + subme)
-    cm, c0 = rc.cost_mv()
+    pos, par, mvc = jobs if jobs is not None else sc.jobs(W // 16, H // 16, nframes, i_pixel, seed=seed + subme)
+    cm, c0 = cost or rc.cost_mv()
     cmd = torch.from_numpy(cm.view(np.int16)).cuda()
     ext = hip.refine_ext(chroma, cf, 0, weights, fenc_chroma=fenc_c, fenc_chroma_origin=c0_.co,
                          fenc_chroma_stride=c0_.cs, ref_chroma=ref_c, ref_chroma_origin=c0_.co,
@@ -52,9 +55,9 @@ def _run(hip, oracle, bd, cf, W, H, nframes, i_pixel, me_method, subme, me_range
                                          ext=oext, fenc_c=c.fenc_c, fc_origin=c.co, fcs=c.cs, ref_c=c.ref_c,
                                          rc_origin=c.co, rcs=c.cs)
         bad = np.argwhere((got[sel] != want).any(1)).ravel()
-        assert not len(bad), (f, bad[:4], got[sel][bad[:4]], want[bad[:4]])
+        assert not len(bad), (*tag, f, bad[:4], got[sel][bad[:4]], want[bad[:4]])
         badn = np.argwhere((ne[sel] != wne).any(1)).ravel()
-        assert not len(badn), (f, badn[:4], ne[sel][badn[:4]], wne[badn[:4]])
+        assert not len(badn), (*tag, f, badn[:4], ne[sel][badn[:4]], wne[badn[:4]])
     return got, par, ne
 
 
@@ -99,18 +102,19 @@ def test_search_2160p(hip, oracle, bd, me_method):
 INT_MAX = (1 << 31) - 1
 
 
-def _chain(hip, oracle, bd, W, H, i_pixel, me_method, subme, seed, nref=3):
+def _chain(hip, oracle, bd, W, H, i_pixel, me_method, subme, seed, nref=3, mr=None, jobs=None, cost=None, tag=()):
     """x264's default ref = 3 loop (analyse.c:1260-1314): one launch per reference with the
     partition's p_halfpel_thresh chained through them and the i_ref_cost adjustments, the HIP
     threshold / outputs / call counts against the oracle's after every reference; returns how
-    many partitions took the early exit"""
+    many partitions took the early exit.  mr / jobs / cost: the MultiRef, the references' (pos,
+    par, mvc) lists and the mv cost table in place of the seeded ones"""
     cf = 1
-    mr = sc.MultiRef(bd, W, H, cf, seed=seed)
+    mr = mr or sc.MultiRef(bd, W, H, cf, seed=seed)
     rows = mr.fenc_y.size // mr.stride
     crows = mr.fenc_c[0].size // mr.cs
     fenc = _t(mr.fenc_y.reshape(1, rows, -1), bd)
     fenc_c = [_t(mr.fenc_c[0].reshape(1, crows, -1), bd)]
-    cm, c0 = rc.cost_mv()
+    cm, c0 = cost or rc.cost_mv()
     cmd = torch.from_numpy(cm.view(np.int16)).cuda()
     oext = oracle.refine_ext(1, cf, 0, (None, None, None))
     n = len(mr.jobs(0, i_pixel, 0)[0])
@@ -124,7 +128,7 @@ def _chain(hip, oracle, bd, W, H, i_pixel, me_method, subme, seed, nref=3):
         ext = hip.refine_ext(1, cf, 0, (None, None, None), fenc_chroma=fenc_c, fenc_chroma_origin=mr.co,
                              fenc_chroma_stride=mr.cs, ref_chroma=ref_c, ref_chroma_origin=mr.co,
                              ref_chroma_stride=mr.cs)
-        pos, par, mvc = mr.jobs(k, i_pixel, seed=seed + 17 * k)
+        pos, par, mvc = jobs[k] if jobs is not None else mr.jobs(k, i_pixel, seed=seed + 17 * k)
         rcost = np.full(n, 40 if k == 0 else 120, np.int32)
         out = torch.full((n, 4), -7, dtype=torch.int32, device="cuda")
         ne = torch.full((n, 2), -1, dtype=torch.int32, device="cuda")
@@ -138,11 +142,11 @@ def _chain(hip, oracle, bd, W, H, i_pixel, me_method, subme, seed, nref=3):
                                          rcs=mr.cs, thresh=thr, ref_cost=rcost, out_fill=-7)
         got = out.cpu().numpy()
         bad = np.argwhere((got != want).any(1)).ravel()
-        assert not len(bad), (k, bad[:4], got[bad[:4]], want[bad[:4]])
+        assert not len(bad), (*tag, k, bad[:4], got[bad[:4]], want[bad[:4]])
         ne = ne.cpu().numpy()
         badn = np.argwhere((ne != wne).any(1)).ravel()
-        assert not len(badn), (k, badn[:4], ne[badn[:4]], wne[badn[:4]])
-        assert np.array_equal(thr_d.cpu().numpy(), thr), k
+        assert not len(badn), (*tag, k, badn[:4], ne[badn[:4]], wne[badn[:4]])
+        assert np.array_equal(thr_d.cpu().numpy(), thr), (*tag, k)
         early += int((want[:, 3] == -7).sum())
     return early, n
 

@@ -26,7 +26,7 @@ def _t(a, bd):
 
 
 def _run(hip, oracle, bd, W, H, nframes, i_pixel, subme, me_range, fade, chroma, seed, cases=None, jobs=None,
-         cost=None, subset=False):
+         cost=None, subset=False, tag=()):
     """test_gpu_search._run for the TESA entry: nframes ChromaCase pairs in one launch"""
     cf = 1
     weights = rc.FADE_WEIGHTS if fade else (None, None, None)
@@ -64,7 +64,7 @@ def _run(hip, oracle, bd, W, H, nframes, i_pixel, subme, me_range, fade, chroma,
                                        mvc[sel], cm, c0, oi, weights, chroma, cf)
         for name, g, w in (("scan", scan[sel], wscan), ("nevals", ne[sel], wne), ("out", got[sel], want)):
             bad = np.argwhere((g != w).any(1)).ravel()
-            assert not len(bad), (name, f, bad[:4], g[bad[:4]], w[bad[:4]])
+            assert not len(bad), (*tag, name, f, bad[:4], g[bad[:4]], w[bad[:4]])
     return got, pos, par, mvc, scan
 
 

@@ -282,6 +282,20 @@ template <int BD> __device__ __forceinline__ int clip_pix( int v )
     return v < 0 ? 0 : v > PT<BD>::PIXEL_MAX ? PT<BD>::PIXEL_MAX : v;
 }
 
+// clip( v >> S ) to a pixel, written as a clamp before the shift.  The form
+// clip( v >> S ) packed into bytes is lowered by this ROCm's compiler to
+// v_ashr_pk_u8_i32, whose packed result came back with the high half not
+// cleared on the box (the hpel filter: bytes 2-3 of every stored dword corrupted;
+// the bidir refine's weighted average: negative sums left garbage in the bytes the
+// compiler ORs the next pair into); the clamp-first form computes the same value and
+// avoids that lowering.
+template <int BD, int S>
+__device__ __forceinline__ int shr_clip( int v )
+{
+    constexpr int HI = (PT<BD>::PIXEL_MAX << S) | ((1 << S) - 1);
+    return (v < 0 ? 0 : v > HI ? HI : v) >> S;
+}
+
 // k-th pixel of a packed dword
 template <int BD> __device__ __forceinline__ int upix( uint32_t w, int k )
 {

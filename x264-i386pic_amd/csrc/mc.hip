@@ -30,18 +30,7 @@ __device__ __forceinline__ int tap6( int a, int b, int c, int d, int e, int f )
 // at 8 bit), and the expand pass with its read-back disappears.
 constexpr int HF_W = 64, HF_H = 16, HF_SW = 76, HF_SH = HF_H + 5;   // SW: 4..7 px of alignment + 64 + 2 + 3 halo
 
-// clip( v >> S ) to a pixel, written as a clamp before the shift.  The form
-// clip( v >> S ) packed into bytes is lowered by this ROCm's compiler to
-// v_ashr_pk_u8_i32, whose packed result came back with the high half not
-// cleared on the box (bytes 2-3 of every stored dword corrupted); the
-// clamp-first form computes the same value and avoids that lowering.
-template <int BD, int S>
-__device__ __forceinline__ int shr_clip( int v )
-{
-    constexpr int HI = (PT<BD>::PIXEL_MAX << S) | ((1 << S) - 1);
-    return (v < 0 ? 0 : v > HI ? HI : v) >> S;
-}
-
+// (shr_clip: hipcommon.h)
 template <int BD>
 __global__ __launch_bounds__( 256 ) void hpel_fused_kernel( const typename PT<BD>::pixel *__restrict__ src,
                                                             typename PT<BD>::pixel *__restrict__ dh,

@@ -2414,8 +2414,13 @@ __global__ __launch_bounds__( 256 ) void me_esa8_kernel( const typename PT<BD>::
     else if( !spare )
         for( int e = lane; e < W * 8; e += 2 * G )
             row_term( e >> 3, e & 7 );
-    // column terms C = xcost << 12 | (mx - min_x) inside the window's columns, 0xF0000000 outside
-    // (the same clamped, branch-free read)
+    // column terms C = xcost << 12 | (mx - min_x) inside the window's columns, COL_OUT outside
+    // (the same clamped, branch-free read).  A key is sad << 12 plus C plus the row term, and a
+    // partition's key is below 2^30 (cost < 2^18), so a column outside must stay at or above
+    // COL_OUT without wrapping: 8 bit adds at most 32640 << 12 to it; 10 bit adds a 16x8 / 8x16
+    // sum of up to 130944 << 12 = 0x1FF80000, which wrapped 0xF0000000 to a small key that won
+    // the minimum (fenc all 1023 on a zero reference: cost 65408 for 130944), hence 0xC0000000
+    constexpr uint32_t COL_OUT = BD == 8 ? 0xF0000000u : 0xC0000000u;
     uint32_t C[4][CPG];
 #pragma unroll
     for( int sl = 0; sl < 4; sl++ )
@@ -2430,7 +2435,7 @@ __global__ __launch_bounds__( 256 ) void me_esa8_kernel( const typename PT<BD>::
             const bool in = mx >= w.x && mx < w.x + w.w;
             const int ci = w.w > 0 ? 4 * min( max( mx, w.x ), w.x + w.w - 1 ) - mvpx : 0;
             const uint32_t t = ((uint32_t)cost_mv[ci] << 12) + (uint32_t)(mx - w.x);
-            C[sl][k] = in ? t : 0xF0000000u;
+            C[sl][k] = in ? t : COL_OUT;
         }
     }
     __syncthreads();
@@ -2526,7 +2531,7 @@ __global__ __launch_bounds__( 256 ) void me_esa8_kernel( const typename PT<BD>::
         if( live )
 #pragma unroll
             for( int sl = 0; sl < 4; sl++ )
-                if( key[sl] < 0xF0000000u )
+                if( key[sl] < COL_OUT )
                     atomicMin( &s_key[lmb * 8 + esa8_part( h, sl )], key[sl] );
     }
     __syncthreads();

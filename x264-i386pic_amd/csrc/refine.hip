@@ -1807,8 +1807,8 @@ __global__ __launch_bounds__( 256 ) void me_refine_bidir_kernel(
                             uint32_t o = 0;
 #pragma unroll
                             for( int e = 0; e < PPD; e++ )
-                                o |= (uint32_t)clip_pix<BD>( (upix<BD>( t0[y][k], e ) * w1 + upix<BD>( t1[y][k], e ) * w2 +
-                                                              32) >> 6 ) << ((32 / PPD) * e);
+                                o |= (uint32_t)shr_clip<BD, 6>( upix<BD>( t0[y][k], e ) * w1 +
+                                                                upix<BD>( t1[y][k], e ) * w2 + 32 ) << ((32 / PPD) * e);
                             t0[y][k] = o;
                         }
                 }
