@@ -1,6 +1,7 @@
 """CPU: the C ABI boundary.
 
 * libx264hip.so loads and exports every function include/x264hip.h declares;
+* the Python binding's ctypes signatures equal the header's prototypes;
 * the re-declared tables have the reference's field order and layout (checked
   by compiling the header with gcc and comparing with the ctypes mirror);
 * the host-side CQM restatement in the product equals the oracle's.
@@ -53,6 +54,65 @@ def test_library_loads_and_resolves():
     L = x.lib()
     for n in declared_functions():
         assert getattr(L, n) is not None
+
+
+_SCALARS = {"intptr_t": ctypes.c_ssize_t, "size_t": ctypes.c_size_t, "int64_t": ctypes.c_int64,
+            "uint32_t": ctypes.c_uint32, "int": ctypes.c_int}
+_POINTERS = (ctypes.c_void_p, ctypes.c_char_p)
+
+
+def header_prototypes():
+    """{name: (return type text, [parameter text, ...])} of every x264hip_* function in the
+    header as a C compiler sees it (X264HIP_DECLARE_ENTRIES expanded for both depths)."""
+    src = subprocess.run(["gcc", "-E", "-P", "-I", os.path.join(ROOT, "include"), HEADER],
+                         capture_output=True, text=True, check=True).stdout
+    protos = {}
+    for decl in " ".join(src.split()).split(";"):
+        m = re.fullmatch(r"\s*([\w\s\*]+?)\b(x264hip_\w+)\s*\((.*)\)\s*", decl)
+        if not m:
+            continue
+        ret, name, params = m.group(1).strip(), m.group(2), m.group(3).strip()
+        assert name not in protos, name
+        protos[name] = (ret, [] if params == "void" else [p.strip() for p in params.split(",")])
+    return protos
+
+
+def _ctype_of(text):
+    """The ctypes type(s) that may stand for a C parameter or return type."""
+    if "*" in text or "[" in text:
+        return _POINTERS if re.match(r"const char \*", text) else (ctypes.c_void_p,)
+    ctype = [w for w in text.split() if w != "const"][0]
+    assert ctype in _SCALARS, f"unclassified C type {text!r}"
+    return (_SCALARS[ctype],)
+
+
+def test_ctypes_signatures_match_header():
+    """Every function of the ABI carries, on the loaded library object, the restype and the
+    argtypes its prototype in include/x264hip.h states: a pointer (`*` or `[` in the declarator)
+    is c_void_p (c_char_p for const char *), intptr_t c_ssize_t, size_t c_size_t, int64_t
+    c_int64, uint32_t c_uint32, int c_int, a void return None.  ctypes converts arguments
+    beyond a short argtypes list as C int, so a miscounted list would truncate a stride
+    silently; an undeclared function has argtypes None."""
+    protos = header_prototypes()
+    # the parser must see exactly the functions declared_functions() finds in the header's text
+    assert sorted(protos) == declared_functions()
+    assert len(protos) == 151
+    L = load_package().lib()
+    bad = []
+    for name, (ret, params) in sorted(protos.items()):
+        fn = getattr(L, name)
+        if fn.argtypes is None:
+            bad.append(f"{name}: no argtypes")
+            continue
+        if not (fn.restype is None if ret == "void" else fn.restype in _ctype_of(ret)):
+            bad.append(f"{name}: returns {ret!r}, restype {fn.restype}")
+        if len(fn.argtypes) != len(params):
+            bad.append(f"{name}: {len(params)} parameters, {len(fn.argtypes)} argtypes")
+            continue
+        for i, (p, a) in enumerate(zip(params, fn.argtypes)):
+            if a not in _ctype_of(p):
+                bad.append(f"{name}: parameter {i} {p!r} has {a.__name__}")
+    assert not bad, "\n".join(bad)
 
 
 def test_library_is_gfx950_code():

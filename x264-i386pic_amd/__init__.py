@@ -334,123 +334,120 @@ def cqm_dequant(scaling_lists, transform_8x8=True):
 
 
 # ----------------------------------------------------------------- declarations
+# Every function of include/x264hip.h, once: "return:parameters", one letter each, in the
+# struct module's spelling where it has one.  tests/test_abi.py checks both tables against
+# the header's prototypes.
+_KINDS = {"P": _P,             # any pointer or array parameter
+          "n": _IP,            # intptr_t
+          "i": _c.c_int,
+          "I": _c.c_uint32,
+          "N": _c.c_size_t,
+          "q": _c.c_int64,
+          "s": _c.c_char_p,    # const char *
+          "v": None}           # void (return only)
+# x264hip_<name>
+_PLAIN = {
+    "init": "i:i",
+    "last_error": "s:",
+    "available": "i:",
+    "set_thread_device": "i:i",
+    "thread_device": "i:",
+    "forward_ref": "i:PiPiNP",
+    "upload": "i:PPNP",
+    "upload_plane": "i:PnPniiiiiP",
+    "upload_planes": "i:iPP",
+    "stream_pair_create": "i:iPP",
+    "stream_destroy": "i:P",
+    "trim": "i:i",
+    "lowres_status": "i:P",
+    "me_table_pitch": "i:iii",
+    "backend_banner": "s:",
+    "set_variant": "i:si",
+    "me_unbind": "v:",
+    "me_bind_stats": "v:PPi",
+    "cqm_dequant": "v:PiPP",
+}
+# x264hip_8_<name> and x264hip_10_<name>
+_PER_DEPTH = {
+    "me_bind": "i:PPniiPi",
+    "me_bind_tables": "i:PPniiPPi",
+    "pixel_init": "v:IP",
+    "pixel_init_hip": "v:P",
+    "dct_init": "v:IP",
+    "dct_init_hip": "v:P",
+    "quant_init": "v:PIP",
+    "quant_init_hip": "v:P",
+    "zigzag_init": "v:IPP",
+    "zigzag_init_hip": "v:PP",
+    "cqm_init": "i:PiiiPPPP",
+    "pixel_cmp_batch": "i:iiPnPnPPiPP",
+    "pixel_stat_batch": "i:iiPnPnPPiiPP",
+    "var2_batch": "i:iPnnPnnPPiPP",
+    "ads_batch": "i:iPPiPPPPPiPiPP",
+    "intra_cmp_x3_batch": "i:iiPnPnPPiPP",
+    "lowres_intra_cost": "i:PnniiiiiiPPPPP",
+    "lowres_inter_cost": "i:PnPPPPnniiiiiiiiiPPPPPPPPP",
+    "lowres_inter_cost_ex": "i:PnPPPPnniiiiiiiiiPPPPPPPPPiiiiP",
+    "weight_scale_plane": "i:PnnPnniiiiiiP",
+    "lowres_bidir_cost": "i:PnPPPPnPPPPnniiiiiiiiiPiPPPPPiiPPPPP",
+    "lowres_bidir_cost_ex": "i:PnPPPPnPPPPnniiiiiiiiiPiPPPPPiiPPPPiP",
+    "frame_integral": "i:PnniiiiPnP",
+    "me_search_full": "i:PnnPnniiiiPP",
+    "me_search_full8": "i:PnnPnniiiiPP",
+    "me_search_centred": "i:PnnPnniiiiPPPP",
+    "me_esa_argmin_at": "i:PiiiPPPPPP",
+    "ssd_plane_batch": "i:PnnPnniiiPP",
+    "ssd_nv12_batch": "i:PnnPnniiiPP",
+    "me_search_esa": "i:PnnPnniiiiiPPPPP",
+    "me_search_esa8": "i:PnnPnniiiiiPPPPPP",
+    "me_tesa": "i:PnnPnnPniiiiiPiPPPPPP",
+    "me_esa_argmin": "i:PiiiPPPPP",
+    "hpel_filter": "i:PPPPnniiiP",
+    "subpel_cmp_batch": "i:iiPnPPPPnPPiPP",
+    "subpel_qpel9_batch": "i:iiPnPPPPnPPiPP",
+    "me_refine_subpel": "i:PnnPPPPnniiiiPPPPiPPP",
+    "me_refine_subpel_ex": "i:PnnPPPPnniiiiPPPPiPPPP",
+    "me_refine_qpel_refdupe": "i:PnnPPPPnniiiPPPPiPPPPPP",
+    "me_search_ref": "i:PnnPPPPPnniiiiPPPPiPPPP",
+    "me_analyse_p16x16": "i:PnnPPPPPnniiiiiiiPPiPPPPP",
+    "me_refine_bidir_satd": "i:PnnPPPPPPPPnniiPPPPiPPPP",
+    "me_search_ref_thresh": "i:PnnPPPPPnniiiiPPPPiPPPPPP",
+    "me_search_ref_tesa": "i:PnnPPPPPnnPPniiiPPPPiPPPPPPP",
+    "sub_dct_batch": "i:iPnPnPPiPP",
+    "dc_batch": "i:iPPiP",
+    "quant_batch": "i:iPPPiPP",
+    "quant_dc_batch": "i:iPiiiPP",
+    "mb_dct_quant": "i:iPnnPnniiiPPPPP",
+    "add_idct_batch": "i:iPnPPiP",
+    "dequant_batch": "i:iPPPiP",
+    "idct_dequant_2x4_batch": "i:iPPPPiP",
+    "optimize_chroma_dc_batch": "i:iPPiPP",
+    "denoise_dct_batch": "i:PiiPPP",
+    "coef_stat_batch": "i:iPqiPP",
+    "coeff_level_run_batch": "i:iPqiPPPPP",
+    "zigzag_scan_batch": "i:iiPPiP",
+    "zigzag_sub_batch": "i:iiPPPnPnPPiPP",
+    "zigzag_interleave_batch": "i:PPPiP",
+    "mb_dequant_idct_add": "i:iPiiiPPPnnPnnP",
+    "ssim_wxh": "i:PnPniiPPP",
+    "ssim_bands": "i:PnnPnniPiiPP",
+    "frame_pixel_stats": "i:PnPPniiiPP",
+    "weight_cost_batch": "i:iPPniiPPiiiiPiPP",
+    "weights_analyse": "i:PPniiPPiPPnPPPPiiiiiiPPPP",
+    "frame_init_lowres": "i:PnniiiPnnP",
+}
+
+
 def _declare(L):
-    L.x264hip_init.argtypes = [_c.c_int]
-    L.x264hip_init.restype = _c.c_int
-    L.x264hip_last_error.restype = _c.c_char_p
-    L.x264hip_available.restype = _c.c_int
-    L.x264hip_set_thread_device.argtypes = [_c.c_int]
-    L.x264hip_set_thread_device.restype = _c.c_int
-    L.x264hip_thread_device.restype = _c.c_int
-    L.x264hip_forward_ref.argtypes = [_P, _c.c_int, _P, _c.c_int, _c.c_size_t, _P]
-    L.x264hip_forward_ref.restype = _c.c_int
-    L.x264hip_upload.argtypes = [_P, _P, _c.c_size_t, _P]
-    L.x264hip_upload.restype = _c.c_int
-    L.x264hip_upload_plane.argtypes = [_P, _IP, _P, _IP, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _P]
-    L.x264hip_upload_plane.restype = _c.c_int
-    L.x264hip_upload_planes.argtypes = [_c.c_int, _P, _P]
-    L.x264hip_upload_planes.restype = _c.c_int
-    L.x264hip_stream_pair_create.argtypes = [_c.c_int, _P, _P]
-    L.x264hip_stream_pair_create.restype = _c.c_int
-    L.x264hip_stream_destroy.argtypes = [_P]
-    L.x264hip_stream_destroy.restype = _c.c_int
-    L.x264hip_backend_banner.restype = _c.c_char_p
-    L.x264hip_set_variant.argtypes = [_c.c_char_p, _c.c_int]
-    L.x264hip_set_variant.restype = _c.c_int
-    L.x264hip_cqm_dequant.argtypes = [_P, _c.c_int, _P, _P]
-    L.x264hip_me_unbind.restype = None
-    L.x264hip_me_bind_stats.argtypes = [_P, _P, _c.c_int]
-    L.x264hip_me_bind_stats.restype = None
-    for bd in (8, 10):
-        f = lambda n: getattr(L, f"x264hip_{bd}_{n}")  # noqa: E731
-        f("me_bind").argtypes = [_P, _P, _IP, _c.c_int, _c.c_int, _P, _c.c_int]
-        f("me_bind").restype = _c.c_int
-        f("me_bind_tables").argtypes = [_P, _P, _IP, _c.c_int, _c.c_int, _P, _P, _c.c_int]
-        f("me_bind_tables").restype = _c.c_int
-        f("pixel_init").argtypes = [_c.c_uint32, _P]
-        f("dct_init").argtypes = [_c.c_uint32, _P]
-        f("quant_init").argtypes = [_P, _c.c_uint32, _P]
-        f("pixel_init_hip").argtypes = [_P]
-        f("dct_init_hip").argtypes = [_P]
-        f("quant_init_hip").argtypes = [_P]
-        f("cqm_init").argtypes = [_P, _c.c_int, _c.c_int, _c.c_int, _P, _P, _P, _P]
-        f("cqm_init").restype = _c.c_int
-        f("pixel_cmp_batch").argtypes = [_c.c_int, _c.c_int, _P, _IP, _P, _IP, _P, _P, _c.c_int, _P, _P]
-        f("me_search_full").argtypes = [_P, _IP, _IP, _P, _IP, _IP, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _P, _P]
-        f("me_search_full8").argtypes = [_P, _IP, _IP, _P, _IP, _IP, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _P, _P]
-        f("me_search_full8").restype = _c.c_int
-        f("sub_dct_batch").argtypes = [_c.c_int, _P, _IP, _P, _IP, _P, _P, _c.c_int, _P, _P]
-        f("dc_batch").argtypes = [_c.c_int, _P, _P, _c.c_int, _P]
-        f("quant_batch").argtypes = [_c.c_int, _P, _P, _P, _c.c_int, _P, _P]
-        f("quant_dc_batch").argtypes = [_c.c_int, _P, _c.c_int, _c.c_int, _c.c_int, _P, _P]
-        f("me_esa_argmin").argtypes = [_P, _c.c_int, _c.c_int, _c.c_int, _P, _P, _P, _P, _P]
-        f("me_esa_argmin_at").argtypes = [_P, _c.c_int, _c.c_int, _c.c_int, _P, _P, _P, _P, _P, _P]
-        f("me_search_centred").argtypes = [_P, _IP, _IP, _P, _IP, _IP, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
-                                           _P, _P, _P, _P]
-        f("me_esa_argmin_at").restype = _c.c_int
-        f("me_tesa").argtypes = [_P, _IP, _IP, _P, _IP, _IP, _P, _IP, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
-                                 _c.c_int, _P, _c.c_int, _P, _P, _P, _P, _P, _P]
-        f("me_tesa").restype = _c.c_int
-        for n in ("ssd_plane_batch", "ssd_nv12_batch"):
-            f(n).argtypes = [_P, _IP, _IP, _P, _IP, _IP, _c.c_int, _c.c_int, _c.c_int, _P, _P]
-            f(n).restype = _c.c_int
-        f("me_search_centred").restype = _c.c_int
-        f("hpel_filter").argtypes = [_P, _P, _P, _P, _IP, _IP, _c.c_int, _c.c_int, _c.c_int, _P]
-        f("subpel_cmp_batch").argtypes = [_c.c_int, _c.c_int, _P, _IP, _P, _P, _P, _P, _IP, _P, _P, _c.c_int, _P, _P]
-        f("subpel_qpel9_batch").argtypes = [_c.c_int, _c.c_int, _P, _IP, _P, _P, _P, _P, _IP, _P, _P, _c.c_int, _P,
-                                            _P]
-        f("subpel_qpel9_batch").restype = _c.c_int
-        f("mb_dct_quant").argtypes = [_c.c_int, _P, _IP, _IP, _P, _IP, _IP, _c.c_int, _c.c_int, _c.c_int,
-                                      _P, _P, _P, _P, _P]
-        f("pixel_stat_batch").argtypes = [_c.c_int, _c.c_int, _P, _IP, _P, _IP, _P, _P, _c.c_int, _c.c_int, _P, _P]
-        f("var2_batch").argtypes = [_c.c_int, _P, _IP, _IP, _P, _IP, _IP, _P, _P, _c.c_int, _P, _P]
-        f("ads_batch").argtypes = [_c.c_int, _P, _P, _c.c_int, _P, _P, _P, _P, _P, _c.c_int, _P, _c.c_int, _P, _P]
-        f("frame_integral").argtypes = [_P, _IP, _IP, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _P, _IP, _P]
-        f("zigzag_init").argtypes = [_c.c_uint32, _P, _P]
-        f("zigzag_init_hip").argtypes = [_P, _P]
-        f("add_idct_batch").argtypes = [_c.c_int, _P, _IP, _P, _P, _c.c_int, _P]
-        f("dequant_batch").argtypes = [_c.c_int, _P, _P, _P, _c.c_int, _P]
-        f("idct_dequant_2x4_batch").argtypes = [_c.c_int, _P, _P, _P, _P, _c.c_int, _P]
-        f("optimize_chroma_dc_batch").argtypes = [_c.c_int, _P, _P, _c.c_int, _P, _P]
-        f("denoise_dct_batch").argtypes = [_P, _c.c_int, _c.c_int, _P, _P, _P]
-        f("coef_stat_batch").argtypes = [_c.c_int, _P, _c.c_int64, _c.c_int, _P, _P]
-        f("coeff_level_run_batch").argtypes = [_c.c_int, _P, _c.c_int64, _c.c_int, _P, _P, _P, _P, _P]
-        f("zigzag_scan_batch").argtypes = [_c.c_int, _c.c_int, _P, _P, _c.c_int, _P]
-        f("zigzag_sub_batch").argtypes = [_c.c_int, _c.c_int, _P, _P, _P, _IP, _P, _IP, _P, _P, _c.c_int, _P, _P]
-        f("zigzag_interleave_batch").argtypes = [_P, _P, _P, _c.c_int, _P]
-        f("frame_init_lowres").argtypes = [_P, _IP, _IP, _c.c_int, _c.c_int, _c.c_int, _P, _IP, _IP, _P]
-        f("frame_init_lowres").restype = _c.c_int
-        f("intra_cmp_x3_batch").argtypes = [_c.c_int, _c.c_int, _P, _IP, _P, _IP, _P, _P, _c.c_int, _P, _P]
-        f("intra_cmp_x3_batch").restype = _c.c_int
-        f("lowres_intra_cost").argtypes = [_P, _IP, _IP, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
-                                           _c.c_int, _P, _P, _P, _P, _P]
-        f("lowres_intra_cost").restype = _c.c_int
-        f("lowres_inter_cost").argtypes = [_P, _IP, _P, _P, _P, _P, _IP, _IP, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
-                                           _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _P, _P, _P, _P, _P, _P,
-                                           _P, _P, _P]
-        f("lowres_inter_cost").restype = _c.c_int
-        f("lowres_inter_cost_ex").argtypes = f("lowres_inter_cost").argtypes[:-1] + [_P, _c.c_int, _c.c_int,
-                                                                                    _c.c_int, _c.c_int, _P]
-        f("lowres_inter_cost_ex").restype = _c.c_int
-        f("weight_scale_plane").argtypes = [_P, _IP, _IP, _P, _IP, _IP, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
-                                            _c.c_int, _c.c_int, _P]
-        f("weight_scale_plane").restype = _c.c_int
-        f("lowres_bidir_cost").argtypes = [_P, _IP, _P, _P, _P, _P, _IP, _P, _P, _P, _P, _IP, _IP, _c.c_int,
-                                           _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
-                                           _c.c_int, _P, _c.c_int, _P, _P, _P, _P, _P, _c.c_int, _c.c_int, _P, _P,
-                                           _P, _P, _P]
-        f("lowres_bidir_cost_ex").argtypes = f("lowres_bidir_cost").argtypes[:-1] + [_c.c_int, _P]
-        f("lowres_bidir_cost_ex").restype = _c.c_int
-        f("lowres_bidir_cost").restype = _c.c_int
-        f("mb_dequant_idct_add").argtypes = [_c.c_int, _P, _c.c_int, _c.c_int, _c.c_int, _P, _P, _P, _IP, _IP,
-                                             _P, _IP, _IP, _P]
-        for n in ("add_idct_batch", "dequant_batch", "idct_dequant_2x4_batch", "optimize_chroma_dc_batch",
-                  "denoise_dct_batch", "coef_stat_batch", "coeff_level_run_batch", "zigzag_scan_batch",
-                  "zigzag_sub_batch", "zigzag_interleave_batch", "mb_dequant_idct_add"):
-            f(n).restype = _c.c_int
-        for n in ("pixel_stat_batch", "var2_batch", "ads_batch", "frame_integral", "pixel_cmp_batch", "me_search_full", "me_esa_argmin", "hpel_filter", "subpel_cmp_batch", "sub_dct_batch", "dc_batch", "quant_batch",
-                  "quant_dc_batch", "mb_dct_quant"):
-            f(n).restype = _c.c_int
+    def declare(fn, sig):
+        ret, params = sig.split(":")
+        fn.restype = _KINDS[ret]
+        fn.argtypes = [_KINDS[k] for k in params]
+    for name, sig in _PLAIN.items():
+        declare(getattr(L, f"x264hip_{name}"), sig)
+    for name, sig in _PER_DEPTH.items():
+        for bd in (8, 10):
+            declare(getattr(L, f"x264hip_{bd}_{name}"), sig)
 
 
 # ----------------------------------------------------------------- CQM
@@ -887,7 +884,6 @@ def ssim_wxh(pix1, origin1, stride1, pix2, origin2, stride2, width, height):
     out = torch.empty(1, dtype=torch.float32, device=pix1.device)
     cnt = _c.c_int(0)
     f = getattr(lib(), f"x264hip_{bd}_ssim_wxh")
-    f.argtypes = [_P, _IP, _P, _IP, _c.c_int, _c.c_int, _P, _P, _P]
     _rc(f(_ptr(pix1, origin1), stride1, _ptr(pix2, origin2), stride2, width, height, _ptr(out), _c.byref(cnt),
           _stream()), "ssim_wxh")
     return float(out.item()), cnt.value
@@ -922,7 +918,6 @@ def ssim_bands(pix1, origin1, stride1, pix2, origin2, stride2, width, bands, out
     if out is None:
         out = torch.empty((nf, nb), dtype=torch.float32, device=pix1.device)
     f = getattr(lib(), f"x264hip_{bd}_ssim_bands")
-    f.argtypes = [_P, _IP, _IP, _P, _IP, _IP, _c.c_int, _P, _c.c_int, _c.c_int, _P, _P]
     f1 = pix1.stride(0) if pix1.dim() == 3 else 0
     f2 = pix2.stride(0) if pix2.dim() == 3 else 0
     _rc(f(_ptr(pix1, origin1), stride1, f1, _ptr(pix2, origin2), stride2, f2, width, _ptr(bands), nb, nf, _ptr(out),
@@ -939,7 +934,6 @@ def frame_pixel_stats(luma, luma_origin, luma_stride, mb_width, mb_height, chrom
     if out is None:
         out = torch.empty(6, dtype=torch.int64, device=luma.device)
     f = getattr(lib(), f"x264hip_{bd}_frame_pixel_stats")
-    f.argtypes = [_P, _IP, _P, _P, _IP, _c.c_int, _c.c_int, _c.c_int, _P, _P]
     _rc(f(_ptr(luma, luma_origin), luma_stride, _plane_ptr(chroma_u, chroma_origin),
           _plane_ptr(chroma_v, chroma_origin), chroma_stride, mb_width, mb_height, chroma_format, _ptr(out),
           _stream()), "frame_pixel_stats")
@@ -965,8 +959,6 @@ def weight_cost_batch(kind, fenc, refs, origin, stride, mb_width, mb_height, can
         out = torch.empty(max(1, n), dtype=torch.int32, device=fenc.device)
     rp = (_P * 4)(*([r.data_ptr() + origin * r.element_size() for r in refs] + [None] * (4 - len(refs))))
     f = getattr(lib(), f"x264hip_{bd}_weight_cost_batch")
-    f.argtypes = [_c.c_int, _P, _P, _IP, _c.c_int, _c.c_int, _P, _P, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _P,
-                  _c.c_int, _P, _P]
     _rc(f(kind, _ptr(fenc, origin), rp, stride, mb_width, mb_height,
           None if intra_cost is None else _ptr(intra_cost), None if mvs is None else _ptr(mvs), int(bool(satd)),
           plane, lam, n_slices, _weights(cands), n, _ptr(out), _stream()), "weight_cost_batch")
@@ -994,8 +986,6 @@ def weights_analyse(fenc_lowres, ref_lowres, lowres_stride, mb_width, mb_height,
     w = (Weight * 3)()
     cd = _c.c_float(-1.0)
     f = getattr(lib(), f"x264hip_{bd}_weights_analyse")
-    f.argtypes = [_P, _P, _IP, _c.c_int, _c.c_int, _P, _P, _c.c_int, _P, _P, _IP, _P, _P, _P, _P, _c.c_int,
-                  _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _P, _P, _P, _P]
     _rc(f(_ptr(fenc_lowres, o), rl, lowres_stride, mb_width, mb_height, _ptr(intra_cost),
           None if mvs is None else _ptr(mvs), chroma_format, fc, rc, chroma_stride, fsum, fssd, rsum, rssd,
           int(bool(b_lookahead)), subme, int(bool(satd)), lam, n_slices, int(bool(weightp_fake)),
@@ -1008,7 +998,6 @@ def lowres_status():
     """Wait for the current stream; raise if a lookahead launch of this thread on its device
     timed out in the band wavefront (x264hip_lowres_status; reporting clears it)."""
     f = lib().x264hip_lowres_status
-    f.argtypes, f.restype = [_P], _c.c_int
     _rc(f(_stream()), "lowres_status")
 
 
@@ -1298,15 +1287,10 @@ def me_refine_subpel(fenc, fenc_origin, fenc_stride, planes, ref_origin, ref_str
     args = [_ptr(fenc, fenc_origin), fenc_stride, ffs, *[_ptr(p, ref_origin) for p in planes], ref_stride, rfs,
             i_pixel, subme, int(bool(refine_qpel)), int(bool(fpel_satd)), _ptr(pos), _ptr(par), _ptr(init_cost),
             _ptr(cm, c0), n, _ptr(out), _ptr(nevals) if nevals is not None else None]
-    types = [_P, _IP, _IP, _P, _P, _P, _P, _IP, _IP, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _P, _P, _P, _P,
-             _c.c_int, _P, _P]
     name = f"x264hip_{bd}_me_refine_subpel" + ("_ex" if ext is not None else "")
     if ext is not None:
         args.append(_c.byref(ext))
-        types.append(_P)
     fn = getattr(lib(), name)
-    fn.argtypes = types + [_P]
-    fn.restype = _c.c_int
     _rc(fn(*args, _stream()), name)
     return out
 
@@ -1335,9 +1319,6 @@ def me_search_ref(fenc, fenc_origin, fenc_stride, fpel_w, planes, ref_origin, re
     thr = halfpel_thresh is not None
     name = f"x264hip_{bd}_me_search_ref" + ("_thresh" if thr else "")
     fn = getattr(lib(), name)
-    fn.argtypes = [_P, _IP, _IP, _P, _P, _P, _P, _P, _IP, _IP, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _P, _P, _P,
-                   _P, _c.c_int, _P, _P] + ([_P, _P] if thr else []) + [_P, _P]
-    fn.restype = _c.c_int
     extra = [_ptr(halfpel_thresh), _ptr(ref_cost) if ref_cost is not None else None] if thr else []
     _rc(fn(_ptr(fenc, fenc_origin), fenc_stride, ffs, _ptr(fpel_w, ref_origin), *[_ptr(p, ref_origin) for p in planes],
            ref_stride, rfs, i_pixel, me_method, subme, me_range, _ptr(pos), _ptr(par), _ptr(mvc), _ptr(cm, c0), n,
@@ -1370,9 +1351,6 @@ def me_search_ref_tesa(fenc, fenc_origin, fenc_stride, fpel_w, planes, ref_origi
     cm, c0 = cost_mv_center
     name = f"x264hip_{bd}_me_search_ref_tesa"
     fn = getattr(lib(), name)
-    fn.argtypes = [_P, _IP, _IP, _P, _P, _P, _P, _P, _IP, _IP, _P, _P, _IP, _c.c_int, _c.c_int, _c.c_int, _P, _P, _P,
-                   _P, _c.c_int, _P, _P, _P, _P, _P, _P, _P]
-    fn.restype = _c.c_int
     opt = lambda t: _ptr(t) if t is not None else None
     _rc(fn(_ptr(fenc, fenc_origin), fenc_stride, ffs, _ptr(fpel_w, ref_origin), *[_ptr(p, ref_origin) for p in planes],
            ref_stride, rfs, _ptr(integral, io), i4, integral[0].numel() if integral.dim() == 3 else 0, i_pixel, subme,
@@ -1398,9 +1376,6 @@ def me_analyse_p16x16(fenc, fenc_origin, fenc_stride, fpel_w, planes, ref_origin
     rfs = ref_frame_stride if ref_frame_stride is not None else _frame_stride(fpel_w, *planes)
     cm, c0 = cost_mv_center
     fn = getattr(lib(), f"x264hip_{bd}_me_analyse_p16x16")
-    fn.argtypes = [_P, _IP, _IP, _P, _P, _P, _P, _P, _IP, _IP] + [_c.c_int] * 7 + [_P, _P, _c.c_int, _P, _P, _P, _P,
-                                                                                   _P]
-    fn.restype = _c.c_int
     _rc(fn(_ptr(fenc, fenc_origin), fenc_stride, ffs, _ptr(fpel_w, ref_origin), *[_ptr(p, ref_origin) for p in planes],
            ref_stride, rfs, mb_width, mb_height, nframes, me_method, subme, me_range, mv_range,
            _ptr(lowres_mv) if lowres_mv is not None else None, _ptr(ref_mv) if ref_mv is not None else None,
@@ -1427,8 +1402,6 @@ def me_refine_bidir(fenc, fenc_origin, fenc_stride, planes0, planes1, ref_origin
     cm, c0 = cost_mv_center
     name = f"x264hip_{bd}_me_refine_bidir_satd"
     fn = getattr(lib(), name)
-    fn.argtypes = [_P, _IP, _IP] + [_P] * 8 + [_IP, _IP, _c.c_int, _c.c_int, _P, _P, _P, _P, _c.c_int, _P, _P, _P, _P]
-    fn.restype = _c.c_int
     _rc(fn(_ptr(fenc, fenc_origin), fenc_stride, ffs, *[_ptr(p, ref_origin) for p in planes0],
            *[_ptr(p, ref_origin) for p in planes1], ref_stride, rfs, i_pixel, int(bool(satd)), _ptr(pos), _ptr(par),
            _ptr(weight), _ptr(cm, c0), n, _ptr(out), _ptr(cost) if cost is not None else None,
@@ -1453,9 +1426,6 @@ def me_refine_qpel_refdupe(fenc, fenc_origin, fenc_stride, planes, ref_origin, r
     cm, c0 = cost_mv_center
     name = f"x264hip_{bd}_me_refine_qpel_refdupe"
     fn = getattr(lib(), name)
-    fn.argtypes = [_P, _IP, _IP, _P, _P, _P, _P, _IP, _IP, _c.c_int, _c.c_int, _c.c_int, _P, _P, _P, _P, _c.c_int,
-                   _P, _P, _P, _P, _P, _P]
-    fn.restype = _c.c_int
     _rc(fn(_ptr(fenc, fenc_origin), fenc_stride, ffs, *[_ptr(p, ref_origin) for p in planes], ref_stride, rfs, i_pixel,
            subme, int(bool(fpel_satd)), _ptr(pos), _ptr(par), _ptr(init_cost), _ptr(cm, c0), n, _ptr(out),
            _ptr(nevals) if nevals is not None else None,
@@ -1580,9 +1550,6 @@ def me_search_esa8(fenc, fenc_origin, fenc_stride, ref, ref_origin, ref_stride, 
     rfs = ref_frame_stride if ref_frame_stride is not None else (ref[0].numel() if ref.dim() == 3 else 0)
     cm, c0 = cost_mv_center
     fn = getattr(lib(), f"x264hip_{bd}_me_search_esa8")
-    fn.argtypes = [_P, _IP, _IP, _P, _IP, _IP, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _P, _P, _P, _P,
-                   _P, _P]
-    fn.restype = _c.c_int
     _rc(fn(_ptr(fenc, fenc_origin), fenc_stride, ffs, _ptr(ref, ref_origin), ref_stride, rfs, mb_width, mb_height,
            nframes, rng, me_range, None if centre is None else _ptr(centre), _ptr(par), _ptr(init_cost),
            _ptr(cm, c0), _ptr(out), _stream()), "me_search_esa8")
@@ -1603,8 +1570,6 @@ def me_search_esa(fenc, fenc_origin, fenc_stride, ref, ref_origin, ref_stride, m
     rfs = ref_frame_stride if ref_frame_stride is not None else (ref[0].numel() if ref.dim() == 3 else 0)
     cm, c0 = cost_mv_center
     fn = getattr(lib(), f"x264hip_{bd}_me_search_esa")
-    fn.argtypes = [_P, _IP, _IP, _P, _IP, _IP, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _P, _P, _P, _P, _P]
-    fn.restype = _c.c_int
     _rc(fn(_ptr(fenc, fenc_origin), fenc_stride, ffs, _ptr(ref, ref_origin), ref_stride, rfs, mb_width, mb_height,
            nframes, rng, me_range, _ptr(par), _ptr(init_cost), _ptr(cm, c0), _ptr(out), _stream()), "me_search_esa")
     return out

@@ -842,17 +842,9 @@ hipError_t launch_mb_dct_quant( int transform, const typename PT<BD>::pixel *fen
     return hipGetLastError();
 }
 
-#define INST( BD )                                                                                                 \
-    template hipError_t launch_sub_dct<BD>( int, const PT<BD>::pixel *, intptr_t, const PT<BD>::pixel *, intptr_t, \
-                                            const int64_t *, const int64_t *, int, PT<BD>::dctcoef *, hipStream_t ); \
-    template hipError_t launch_dc<BD>( int, PT<BD>::dctcoef *, PT<BD>::dctcoef *, int, hipStream_t );             \
-    template hipError_t launch_quant<BD>( int, PT<BD>::dctcoef *, const PT<BD>::udctcoef *,                        \
-                                          const PT<BD>::udctcoef *, int, int, int, int32_t *, hipStream_t );        \
-    template hipError_t launch_mb_dct_quant<BD>( int, const PT<BD>::pixel *, intptr_t, intptr_t,                   \
-                                                 const PT<BD>::pixel *, intptr_t, intptr_t, int, int, int,        \
-                                                 const PT<BD>::udctcoef *, const PT<BD>::udctcoef *,              \
-                                                 PT<BD>::dctcoef *, int32_t *, hipStream_t );
-INST( 8 )
-INST( 10 )
+X264HIP_INSTANTIATE( launch_sub_dct );
+X264HIP_INSTANTIATE( launch_dc );
+X264HIP_INSTANTIATE( launch_quant );
+X264HIP_INSTANTIATE( launch_mb_dct_quant );
 
 } // namespace x264hip

@@ -384,6 +384,10 @@ inline hipError_t stream_device( hipStream_t stream, int *dev )
 } // namespace x264hip
 
 // ---- launchers implemented in the .hip files (all enqueue on `stream`) ----
+// A .hip file instantiates each launcher it defines with these, from the type declared below:
+// for one bit depth, or (the usual case) for both
+#define X264HIP_INSTANTIATE_BD( fn, bd ) template decltype( fn<bd> ) fn<bd>
+#define X264HIP_INSTANTIATE( fn ) X264HIP_INSTANTIATE_BD( fn, 8 ); X264HIP_INSTANTIATE_BD( fn, 10 )
 namespace x264hip {
 hipError_t scratch_trim( int dev );
 hipError_t scratch_alloc( void **p, size_t bytes, hipStream_t stream );   // free with hipFreeAsync

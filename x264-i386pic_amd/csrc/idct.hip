@@ -1216,31 +1216,21 @@ hipError_t launch_mb_recon( int transform, const typename PT<BD>::dctcoef *dct, 
     return hipGetLastError();
 }
 
-#define INST( BD )                                                                                                     \
-    template hipError_t launch_add_idct<BD>( int, PT<BD>::pixel *, intptr_t, const int64_t *, const PT<BD>::dctcoef *, \
-                                             int, hipStream_t );                                                       \
-    template hipError_t launch_dequant<BD>( int, PT<BD>::dctcoef *, const int32_t *, const int32_t *, int,             \
-                                            hipStream_t );                                                             \
-    template hipError_t launch_idct4x4dc<BD>( PT<BD>::dctcoef *, int, hipStream_t );                                   \
-    template hipError_t launch_idct_dequant_2x4<BD>( int, PT<BD>::dctcoef *, PT<BD>::dctcoef *, const int32_t *,       \
-                                                     const int32_t *, int, hipStream_t );                              \
-    template hipError_t launch_optimize_chroma<BD>( int, PT<BD>::dctcoef *, const int32_t *, int, int32_t *,           \
-                                                    hipStream_t );                                                     \
-    template hipError_t launch_denoise<BD>( PT<BD>::dctcoef *, int, int, uint32_t *, const PT<BD>::udctcoef *,         \
-                                            hipStream_t );                                                             \
-    template hipError_t launch_coef_stat<BD>( int, const PT<BD>::dctcoef *, int64_t, int, int32_t *, hipStream_t );    \
-    template hipError_t launch_level_run<BD>( int, const PT<BD>::dctcoef *, int64_t, int, int32_t *, int32_t *,        \
-                                              int32_t *, PT<BD>::dctcoef *, hipStream_t );                             \
-    template hipError_t launch_zigzag_scan<BD>( int, int, PT<BD>::dctcoef *, const PT<BD>::dctcoef *, int,             \
-                                                hipStream_t );                                                         \
-    template hipError_t launch_zigzag_sub<BD>( int, int, PT<BD>::dctcoef *, PT<BD>::dctcoef *, const PT<BD>::pixel *,  \
-                                               intptr_t, PT<BD>::pixel *, intptr_t, const int64_t *, const int64_t *,  \
-                                               int, int32_t *, hipStream_t );                                          \
-    template hipError_t launch_interleave<BD>( PT<BD>::dctcoef *, const PT<BD>::dctcoef *, uint8_t *, int,             \
-                                               hipStream_t );                                                          \
-    template hipError_t launch_mb_recon<BD>( int, const PT<BD>::dctcoef *, int, int, int, const int32_t *,             \
-                                             const int32_t *, const PT<BD>::pixel *, intptr_t, intptr_t,               \
-                                             PT<BD>::pixel *, intptr_t, intptr_t, hipStream_t );
+// All of depth 8, then all of depth 10 (X264HIP_INSTANTIATE would alternate): the order of
+// instantiation is the order of this file's kernels and their constant tables in the code object
+#define INST( BD )                                         \
+    X264HIP_INSTANTIATE_BD( launch_add_idct, BD );         \
+    X264HIP_INSTANTIATE_BD( launch_dequant, BD );          \
+    X264HIP_INSTANTIATE_BD( launch_idct4x4dc, BD );        \
+    X264HIP_INSTANTIATE_BD( launch_idct_dequant_2x4, BD ); \
+    X264HIP_INSTANTIATE_BD( launch_optimize_chroma, BD );  \
+    X264HIP_INSTANTIATE_BD( launch_denoise, BD );          \
+    X264HIP_INSTANTIATE_BD( launch_coef_stat, BD );        \
+    X264HIP_INSTANTIATE_BD( launch_level_run, BD );        \
+    X264HIP_INSTANTIATE_BD( launch_zigzag_scan, BD );      \
+    X264HIP_INSTANTIATE_BD( launch_zigzag_sub, BD );       \
+    X264HIP_INSTANTIATE_BD( launch_interleave, BD );       \
+    X264HIP_INSTANTIATE_BD( launch_mb_recon, BD );
 INST( 8 )
 INST( 10 )
 #undef INST

@@ -556,14 +556,7 @@ hipError_t launch_intra_x3( int kind, int op, const typename PT<BD>::pixel *fenc
     return hipGetLastError();
 }
 
-#define INST( BD )                                                                                                   \
-    template hipError_t launch_lowres_intra<BD>( const PT<BD>::pixel *, intptr_t, intptr_t, int, int, int, int, int,  \
-                                                 int, const uint16_t *, uint16_t *, int32_t *, int32_t *,             \
-                                                 hipStream_t );                                                       \
-    template hipError_t launch_intra_x3<BD>( int, int, const PT<BD>::pixel *, intptr_t, const PT<BD>::pixel *,      \
-                                             intptr_t, const int64_t *, const int64_t *, int, int32_t *, hipStream_t );
-INST( 8 )
-INST( 10 )
-#undef INST
+X264HIP_INSTANTIATE( launch_lowres_intra );
+X264HIP_INSTANTIATE( launch_intra_x3 );
 
 } // namespace x264hip

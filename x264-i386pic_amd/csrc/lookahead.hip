@@ -1886,24 +1886,7 @@ hipError_t launch_lowres_inter( const typename PT<BD>::pixel *fenc, intptr_t ffs
     return la_status_end( stream );
 }
 
-#define INST( BD )                                                                                              \
-    template hipError_t launch_lowres_inter<BD>( const PT<BD>::pixel *, intptr_t, const PT<BD>::pixel *const[4], \
-                                                 intptr_t, intptr_t, int, int, int, int, int, int, int, int, int, \
-                                                 const uint16_t *, const uint16_t *, const uint16_t *, int16_t *, \
-                                                 int32_t *, uint16_t *, int32_t *, int32_t *,                     \
-                                                 const PT<BD>::pixel *, int, int, int, int, hipStream_t );
-INST( 8 )
-INST( 10 )
-#undef INST
-#define INST( BD )                                                                                              \
-    template hipError_t launch_lowres_bidir<BD>( const PT<BD>::pixel *, intptr_t, const PT<BD>::pixel *const[4], \
-                                                 intptr_t, const PT<BD>::pixel *const[4], intptr_t, intptr_t, int,  \
-                                                 int, int, int, int, int, int, int, int, const uint16_t *, int,     \
-                                                 int16_t *, int32_t *, int16_t *, int32_t *, const int16_t *, int,  \
-                                                 int, const uint16_t *, uint16_t *, int32_t *, int32_t *, int,      \
-                                                 hipStream_t );
-INST( 8 )
-INST( 10 )
-#undef INST
+X264HIP_INSTANTIATE( launch_lowres_inter );
+X264HIP_INSTANTIATE( launch_lowres_bidir );
 
 } // namespace x264hip

@@ -1277,19 +1277,10 @@ hipError_t launch_frame_init_lowres( const typename PT<BD>::pixel *src, intptr_t
     return hipGetLastError();
 }
 
-#define INST( BD )                                                                                              \
-    template hipError_t launch_hpel_filter<BD>( const PT<BD>::pixel *, PT<BD>::pixel *, PT<BD>::pixel *,       \
-                                                PT<BD>::pixel *, intptr_t, intptr_t, int, int, int, hipStream_t ); \
-    template hipError_t launch_subpel_cmp<BD>( int, int, const PT<BD>::pixel *, intptr_t,                      \
-                                               const PT<BD>::pixel *const[4], intptr_t, const int64_t *,       \
-                                               const int32_t *, int, int32_t *, hipStream_t );      \
-    template hipError_t launch_subpel_qpel9<BD>( int, int, const PT<BD>::pixel *, intptr_t,                    \
-                                                 const PT<BD>::pixel *const[4], intptr_t, const int64_t *,     \
-                                                 const int32_t *, int, int32_t *, hipStream_t );               \
-    template hipError_t launch_frame_init_lowres<BD>( const PT<BD>::pixel *, intptr_t, intptr_t, int, int, int,  \
-                                                      PT<BD>::pixel *const[4], intptr_t, intptr_t, hipStream_t );
-INST( 8 )
-INST( 10 )
+X264HIP_INSTANTIATE( launch_hpel_filter );
+X264HIP_INSTANTIATE( launch_subpel_cmp );
+X264HIP_INSTANTIATE( launch_subpel_qpel9 );
+X264HIP_INSTANTIATE( launch_frame_init_lowres );
 
 } // namespace x264hip
 
@@ -1366,10 +1357,7 @@ hipError_t launch_weight_plane( typename PT<BD>::pixel *dst, intptr_t ds, intptr
                         offset * (1 << (BD - 8)) );
     return hipGetLastError();
 }
-template hipError_t launch_weight_plane<8>( uint8_t *, intptr_t, intptr_t, const uint8_t *, intptr_t, intptr_t, int,
-                                            int, int, int, int, int, hipStream_t );
-template hipError_t launch_weight_plane<10>( uint16_t *, intptr_t, intptr_t, const uint16_t *, intptr_t, intptr_t,
-                                             int, int, int, int, int, int, hipStream_t );
+X264HIP_INSTANTIATE( launch_weight_plane );
 
 // ---------------------------------------------------------------------------
 // A picture plane from page-locked host memory into a padded frame plane: x264_frame_copy_

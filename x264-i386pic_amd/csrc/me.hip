@@ -584,10 +584,7 @@ hipError_t launch_me_full8( const typename PT<BD>::pixel *fenc, intptr_t fs, int
     }
     return hipGetLastError();
 }
-template hipError_t launch_me_full8<8>( const uint8_t *, intptr_t, intptr_t, const uint8_t *, intptr_t, intptr_t, int,
-                                        int, int, int, uint16_t *, hipStream_t );
-template hipError_t launch_me_full8<10>( const uint16_t *, intptr_t, intptr_t, const uint16_t *, intptr_t, intptr_t,
-                                         int, int, int, int, uint16_t *, hipStream_t );
+X264HIP_INSTANTIATE( launch_me_full8 );
 
 // Full-search / centred tables.  The grouped kernels need dword-aligned fenc rows,
 // dword-multiple strides and a dword-aligned ref plane (and, at 8 bit, a lane count below
@@ -638,10 +635,7 @@ hipError_t launch_me_full( const typename PT<BD>::pixel *fenc, intptr_t fs, intp
     return hipGetLastError();
 }
 
-template hipError_t launch_me_full<8>( const uint8_t *, intptr_t, intptr_t, const uint8_t *, intptr_t, intptr_t, int,
-                                       int, int, int, uint16_t *, const int16_t *, int16_t *, hipStream_t );
-template hipError_t launch_me_full<10>( const uint16_t *, intptr_t, intptr_t, const uint16_t *, intptr_t, intptr_t,
-                                        int, int, int, int, uint32_t *, const int16_t *, int16_t *, hipStream_t );
+X264HIP_INSTANTIATE( launch_me_full );
 
 // ---------------------------------------------------------------------------
 // Fused search + ESA decision (8 bit): the four-column lanes of the centred search around
@@ -1025,12 +1019,7 @@ hipError_t launch_me_search_esa( const typename PT<BD>::pixel *fenc, intptr_t fs
     return hipGetLastError();
 }
 
-template hipError_t launch_me_search_esa<8>( const uint8_t *, intptr_t, intptr_t, const uint8_t *, intptr_t, intptr_t,
-                                             int, int, int, int, int, const int16_t *, const int32_t *,
-                                             const uint16_t *, int32_t *, hipStream_t );
-template hipError_t launch_me_search_esa<10>( const uint16_t *, intptr_t, intptr_t, const uint16_t *, intptr_t,
-                                              intptr_t, int, int, int, int, int, const int16_t *, const int32_t *,
-                                              const uint16_t *, int32_t *, hipStream_t );
+X264HIP_INSTANTIATE( launch_me_search_esa );
 
 // ---------------------------------------------------------------------------
 // ESA decision over a table (reference encoder/me.c:618-631 plain exhaustive form, equal
@@ -1253,10 +1242,7 @@ hipError_t launch_me_esa_argmin( const typename PT<BD>::sadt *table, int R, int 
     return hipGetLastError();
 }
 
-template hipError_t launch_me_esa_argmin<8>( const uint16_t *, int, int, int, const int16_t *, const int16_t *,
-                                             const int32_t *, const uint16_t *, int32_t *, hipStream_t );
-template hipError_t launch_me_esa_argmin<10>( const uint32_t *, int, int, int, const int16_t *, const int16_t *,
-                                              const int32_t *, const uint16_t *, int32_t *, hipStream_t );
+X264HIP_INSTANTIATE( launch_me_esa_argmin );
 
 // ---------------------------------------------------------------------------
 // TESA (reference encoder/me.c:653-748) for PIXEL_16x16: one wave per macroblock.
@@ -1998,14 +1984,7 @@ hipError_t launch_me_tesa( const typename PT<BD>::pixel *fenc, intptr_t fs, intp
     return hipGetLastError();
 }
 
-template hipError_t launch_me_tesa<8>( const uint8_t *, intptr_t, intptr_t, const uint8_t *, intptr_t, intptr_t,
-                                       const uint16_t *, intptr_t, int, int, int, int, int, const uint16_t *, int,
-                                       const int16_t *, const int16_t *, const int32_t *, const uint16_t *, int32_t *,
-                                       hipStream_t );
-template hipError_t launch_me_tesa<10>( const uint16_t *, intptr_t, intptr_t, const uint16_t *, intptr_t, intptr_t,
-                                        const uint16_t *, intptr_t, int, int, int, int, int, const uint32_t *, int,
-                                        const int16_t *, const int16_t *, const int32_t *, const uint16_t *,
-                                        int32_t *, hipStream_t );
+X264HIP_INSTANTIATE( launch_me_tesa );
 
 // ---------------------------------------------------------------------------
 // Sub-partition ESA decisions (x264hip_*_me_search_esa8): x264's ESA (encoder/me.c:618-631)
@@ -2631,11 +2610,6 @@ hipError_t launch_me_search_esa8( const typename PT<BD>::pixel *fenc, intptr_t f
     return hipGetLastError();
 }
 
-template hipError_t launch_me_search_esa8<8>( const uint8_t *, intptr_t, intptr_t, const uint8_t *, intptr_t, intptr_t,
-                                              int, int, int, int, int, const int16_t *, const int16_t *,
-                                              const int32_t *, const uint16_t *, int32_t *, hipStream_t );
-template hipError_t launch_me_search_esa8<10>( const uint16_t *, intptr_t, intptr_t, const uint16_t *, intptr_t,
-                                               intptr_t, int, int, int, int, int, const int16_t *, const int16_t *,
-                                               const int32_t *, const uint16_t *, int32_t *, hipStream_t );
+X264HIP_INSTANTIATE( launch_me_search_esa8 );
 
 } // namespace x264hip

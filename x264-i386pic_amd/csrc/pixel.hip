@@ -258,10 +258,7 @@ hipError_t launch_cmp_batch( int op, int i_pixel, const typename PT<BD>::pixel *
     return hipErrorInvalidValue;
 }
 
-template hipError_t launch_cmp_batch<8>( int, int, const uint8_t *, intptr_t, const uint8_t *, intptr_t,
-                                         const int64_t *, const int64_t *, int, int32_t *, hipStream_t );
-template hipError_t launch_cmp_batch<10>( int, int, const uint16_t *, intptr_t, const uint16_t *, intptr_t,
-                                          const int64_t *, const int64_t *, int, int32_t *, hipStream_t );
+X264HIP_INSTANTIATE( launch_cmp_batch );
 
 
 // ---------------------------------------------------------------------------
@@ -770,18 +767,9 @@ hipError_t launch_frame_integral( const typename PT<BD>::pixel *plane, intptr_t 
     return hipGetLastError();
 }
 
-#define INST( BD )                                                                                                     \
-    template hipError_t launch_stat_batch<BD>( int, int, const PT<BD>::pixel *, intptr_t, const PT<BD>::pixel *,       \
-                                               intptr_t, const int64_t *, const int64_t *, int, int, uint64_t *,       \
-                                               hipStream_t );                                                          \
-    template hipError_t launch_var2_batch<BD>( int, const PT<BD>::pixel *, intptr_t, intptr_t, const PT<BD>::pixel *,  \
-                                               intptr_t, intptr_t, const int64_t *, const int64_t *, int, int32_t *,   \
-                                               hipStream_t );                                                          \
-    template hipError_t launch_frame_integral<BD>( const PT<BD>::pixel *, intptr_t, intptr_t, int, int, int, int,      \
-                                                   uint16_t *, intptr_t, hipStream_t );
-INST( 8 )
-INST( 10 )
-#undef INST
+X264HIP_INSTANTIATE( launch_stat_batch );
+X264HIP_INSTANTIATE( launch_var2_batch );
+X264HIP_INSTANTIATE( launch_frame_integral );
 
 } // namespace x264hip
 
@@ -1053,9 +1041,6 @@ hipError_t launch_plane_ssd( int nv12, const typename PT<BD>::pixel *p1, intptr_
     return hipGetLastError();
 }
 
-template hipError_t launch_plane_ssd<8>( int, const uint8_t *, intptr_t, intptr_t, const uint8_t *, intptr_t, intptr_t,
-                                         int, int, int, uint64_t *, hipStream_t );
-template hipError_t launch_plane_ssd<10>( int, const uint16_t *, intptr_t, intptr_t, const uint16_t *, intptr_t,
-                                          intptr_t, int, int, int, uint64_t *, hipStream_t );
+X264HIP_INSTANTIATE( launch_plane_ssd );
 
 } // namespace x264hip

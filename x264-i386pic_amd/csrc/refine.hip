@@ -1579,14 +1579,7 @@ hipError_t launch_me_search_pred( const typename PT<BD>::pixel *fenc, intptr_t f
 #undef SP_GO
     return hipGetLastError();
 }
-template hipError_t launch_me_search_pred<8>( const uint8_t *, intptr_t, intptr_t, const uint8_t *,
-                                              const uint8_t *const[4], intptr_t, intptr_t, int, int, const int32_t *,
-                                              const int16_t *, const int16_t *, const uint16_t *, int, int32_t *,
-                                              const x264hip_refine_ext_t *, hipStream_t );
-template hipError_t launch_me_search_pred<10>( const uint16_t *, intptr_t, intptr_t, const uint16_t *,
-                                               const uint16_t *const[4], intptr_t, intptr_t, int, int,
-                                               const int32_t *, const int16_t *, const int16_t *, const uint16_t *,
-                                               int, int32_t *, const x264hip_refine_ext_t *, hipStream_t );
+X264HIP_INSTANTIATE( launch_me_search_pred );
 
 // x264_me_search_ref's refine after an integer stage that left rpar / rinit (me.c:791-797): nevals
 // (or NULL) points at the partition's second count, two int32 per partition
@@ -1601,16 +1594,7 @@ hipError_t launch_me_search_refine( const typename PT<BD>::pixel *fenc, intptr_t
     return refine_launch<BD>( fenc, fs, ffs, planes, rs, rfs, i_pixel, subme, 0, fpel_satd, pos, rpar, rinit, cost_mv,
                               n, out, nevals, 2, thr, rcost, xe, stream );
 }
-template hipError_t launch_me_search_refine<8>( const uint8_t *, intptr_t, intptr_t, const uint8_t *const[4], intptr_t,
-                                                intptr_t, int, int, int, const int32_t *, const int16_t *,
-                                                const int32_t *, const uint16_t *, int, int32_t *, int32_t *,
-                                                int32_t *, const int32_t *, const x264hip_refine_ext_t *,
-                                                hipStream_t );
-template hipError_t launch_me_search_refine<10>( const uint16_t *, intptr_t, intptr_t, const uint16_t *const[4],
-                                                 intptr_t, intptr_t, int, int, int, const int32_t *, const int16_t *,
-                                                 const int32_t *, const uint16_t *, int, int32_t *, int32_t *,
-                                                 int32_t *, const int32_t *, const x264hip_refine_ext_t *,
-                                                 hipStream_t );
+X264HIP_INSTANTIATE( launch_me_search_refine );
 
 template <int BD>
 hipError_t launch_me_search_ref( const typename PT<BD>::pixel *fenc, intptr_t fs, intptr_t ffs,
@@ -1912,35 +1896,11 @@ hipError_t launch_me_refine_bidir( const typename PT<BD>::pixel *fenc, intptr_t 
 #undef BI_GO
     return hipGetLastError();
 }
-template hipError_t launch_me_refine_bidir<8>( const uint8_t *, intptr_t, intptr_t, const uint8_t *const[4],
-                                               const uint8_t *const[4], intptr_t, intptr_t, int, int, const int32_t *,
-                                               const int16_t *, const int32_t *, const uint16_t *, int, int32_t *,
-                                               int32_t *, int32_t *, hipStream_t );
-template hipError_t launch_me_refine_bidir<10>( const uint16_t *, intptr_t, intptr_t, const uint16_t *const[4],
-                                                const uint16_t *const[4], intptr_t, intptr_t, int, int, const int32_t *,
-                                                const int16_t *, const int32_t *, const uint16_t *, int, int32_t *,
-                                                int32_t *, int32_t *, hipStream_t );
+X264HIP_INSTANTIATE( launch_me_refine_bidir );
 
-template hipError_t launch_me_search_ref<8>( const uint8_t *, intptr_t, intptr_t, const uint8_t *, const uint8_t *const[4],
-                                             intptr_t, intptr_t, int, int, int, int, const int32_t *, const int16_t *,
-                                             const int16_t *, const uint16_t *, int, int32_t *, int32_t *, int32_t *,
-                                             const int32_t *, const x264hip_refine_ext_t *, hipStream_t );
-template hipError_t launch_me_search_ref<10>( const uint16_t *, intptr_t, intptr_t, const uint16_t *,
-                                              const uint16_t *const[4], intptr_t, intptr_t, int, int, int, int,
-                                              const int32_t *, const int16_t *, const int16_t *, const uint16_t *, int,
-                                              int32_t *, int32_t *, int32_t *, const int32_t *, const x264hip_refine_ext_t *,
-                                              hipStream_t );
+X264HIP_INSTANTIATE( launch_me_search_ref );
 
-template hipError_t launch_me_refine_subpel<8>( const uint8_t *, intptr_t, intptr_t, const uint8_t *const[4],
-                                                intptr_t, intptr_t, int, int, int, int, const int32_t *,
-                                                const int16_t *, const int32_t *, const uint16_t *, int, int32_t *,
-                                                int32_t *, int32_t *, const int32_t *, const x264hip_refine_ext_t *,
-                                                hipStream_t );
-template hipError_t launch_me_refine_subpel<10>( const uint16_t *, intptr_t, intptr_t, const uint16_t *const[4],
-                                                 intptr_t, intptr_t, int, int, int, int, const int32_t *,
-                                                 const int16_t *, const int32_t *, const uint16_t *, int, int32_t *,
-                                                 int32_t *, int32_t *, const int32_t *, const x264hip_refine_ext_t *,
-                                                 hipStream_t );
+X264HIP_INSTANTIATE( launch_me_refine_subpel );
 
 // ---------------------------------------------------------------------------
 // x264's P16x16 reference-0 analysis over whole frames with the encoder's own predictors
@@ -2169,14 +2129,6 @@ hipError_t launch_me_analyse_p16x16( const typename PT<BD>::pixel *fenc, intptr_
     const hipError_t fr = hipFreeAsync( buf, stream );
     return e != hipSuccess ? e : fr;
 }
-template hipError_t launch_me_analyse_p16x16<8>( const uint8_t *, intptr_t, intptr_t, const uint8_t *,
-                                                 const uint8_t *const[4], intptr_t, intptr_t, int, int, int, int, int,
-                                                 int, int, const int16_t *, const int16_t *, int, const uint16_t *,
-                                                 int32_t *, int32_t *, const x264hip_refine_ext_t *, hipStream_t );
-template hipError_t launch_me_analyse_p16x16<10>( const uint16_t *, intptr_t, intptr_t, const uint16_t *,
-                                                  const uint16_t *const[4], intptr_t, intptr_t, int, int, int, int,
-                                                  int, int, int, const int16_t *, const int16_t *, int,
-                                                  const uint16_t *, int32_t *, int32_t *, const x264hip_refine_ext_t *,
-                                                  hipStream_t );
+X264HIP_INSTANTIATE( launch_me_analyse_p16x16 );
 
 } // namespace x264hip

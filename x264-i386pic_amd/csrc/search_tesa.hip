@@ -431,17 +431,6 @@ hipError_t launch_me_search_ref_tesa( const typename PT<BD>::pixel *fenc, intptr
     const hipError_t ef = hipFreeAsync( buf, stream );
     return e == hipSuccess ? ef : e;
 }
-template hipError_t launch_me_search_ref_tesa<8>( const uint8_t *, intptr_t, intptr_t, const uint8_t *,
-                                                  const uint8_t *const[4], intptr_t, intptr_t, const uint16_t *,
-                                                  const uint16_t *, intptr_t, int, int, int, const int32_t *,
-                                                  const int16_t *, const int16_t *, const uint16_t *, int, int32_t *,
-                                                  int32_t *, int32_t *, int32_t *, const int32_t *,
-                                                  const x264hip_refine_ext_t *, hipStream_t );
-template hipError_t launch_me_search_ref_tesa<10>( const uint16_t *, intptr_t, intptr_t, const uint16_t *,
-                                                   const uint16_t *const[4], intptr_t, intptr_t, const uint16_t *,
-                                                   const uint16_t *, intptr_t, int, int, int, const int32_t *,
-                                                   const int16_t *, const int16_t *, const uint16_t *, int, int32_t *,
-                                                   int32_t *, int32_t *, int32_t *, const int32_t *,
-                                                   const x264hip_refine_ext_t *, hipStream_t );
+X264HIP_INSTANTIATE( launch_me_search_ref_tesa );
 
 } // namespace x264hip

@@ -176,10 +176,7 @@ hipError_t launch_ssim_wxh( const typename PT<BD>::pixel *p1, intptr_t s1, const
     const hipError_t ef = hipFreeAsync( buf, stream );
     return e != hipSuccess ? e : ef;
 }
-template hipError_t launch_ssim_wxh<8>( const uint8_t *, intptr_t, const uint8_t *, intptr_t, int, int, float *,
-                                        hipStream_t );
-template hipError_t launch_ssim_wxh<10>( const uint16_t *, intptr_t, const uint16_t *, intptr_t, int, int, float *,
-                                         hipStream_t );
+X264HIP_INSTANTIATE( launch_ssim_wxh );
 
 // The encoder's form (encoder.c:2516-2528): x264_pixel_ssim_wxh once per filtered MB-row band,
 // each band's float independent of the others (the encoder adds them in double).  One
@@ -258,10 +255,7 @@ hipError_t launch_ssim_bands( const typename PT<BD>::pixel *p1, intptr_t s1, int
                         p1, s1, f1, p2, s2, f2, nx, (const int2 *)bands, nbands, out );
     return hipGetLastError();
 }
-template hipError_t launch_ssim_bands<8>( const uint8_t *, intptr_t, intptr_t, const uint8_t *, intptr_t, intptr_t, int,
-                                          const int32_t *, int, int, float *, hipStream_t );
-template hipError_t launch_ssim_bands<10>( const uint16_t *, intptr_t, intptr_t, const uint16_t *, intptr_t, intptr_t,
-                                           int, const int32_t *, int, int, float *, hipStream_t );
+X264HIP_INSTANTIATE( launch_ssim_bands );
 
 // the per-call table entries' kernels: ssim_4x4x2_core of one block pair (8 ints out) and
 // ssim_end4 of staged sum rows
@@ -308,9 +302,7 @@ hipError_t launch_ssim_end4( const int *s0, const int *s1, int width, float *out
                         width, out );
     return hipGetLastError();
 }
-template hipError_t launch_ssim_core<8>( const uint8_t *, intptr_t, const uint8_t *, intptr_t, int *, hipStream_t );
-template hipError_t launch_ssim_core<10>( const uint16_t *, intptr_t, const uint16_t *, intptr_t, int *, hipStream_t );
-template hipError_t launch_ssim_end4<8>( const int *, const int *, int, float *, hipStream_t );
-template hipError_t launch_ssim_end4<10>( const int *, const int *, int, float *, hipStream_t );
+X264HIP_INSTANTIATE( launch_ssim_core );
+X264HIP_INSTANTIATE( launch_ssim_end4 );
 
 } // namespace x264hip

@@ -373,12 +373,7 @@ hipError_t launch_weight_cost( int kind, const typename PT<BD>::pixel *fenc, int
     }
     return hipSuccess;
 }
-template hipError_t launch_weight_cost<8>( int, const uint8_t *, intptr_t, const uint8_t *const[4], intptr_t, int, int,
-                                           const uint16_t *, const int16_t *, int, int, int, int,
-                                           const x264hip_weight_t *, int, uint32_t *, hipStream_t );
-template hipError_t launch_weight_cost<10>( int, const uint16_t *, intptr_t, const uint16_t *const[4], intptr_t, int,
-                                            int, const uint16_t *, const int16_t *, int, int, int, int,
-                                            const x264hip_weight_t *, int, uint32_t *, hipStream_t );
+X264HIP_INSTANTIATE( launch_weight_cost );
 
 // ---- frame statistics: ac_energy_mb's stores (ratecontrol.c:225-257, 289-299) ----
 __device__ __forceinline__ unsigned long long wave_sum64( unsigned long long v )
@@ -485,10 +480,7 @@ hipError_t launch_frame_stats( const typename PT<BD>::pixel *y, intptr_t ys, con
                         mbw > 0 ? mbw : 1, mbh > 0 ? mbh : 1, cf );
     return hipGetLastError();
 }
-template hipError_t launch_frame_stats<8>( const uint8_t *, intptr_t, const uint8_t *, const uint8_t *, intptr_t, int,
-                                           int, int, uint64_t *, hipStream_t );
-template hipError_t launch_frame_stats<10>( const uint16_t *, intptr_t, const uint16_t *, const uint16_t *, intptr_t,
-                                            int, int, int, uint64_t *, hipStream_t );
+X264HIP_INSTANTIATE( launch_frame_stats );
 
 // ---- x264_weights_analyse (slicetype.c:284-501): the host walk ----
 #pragma clang fp contract( off )
@@ -773,7 +765,6 @@ hipError_t weights_analyse( const WpInput<BD> &in, x264hip_weight_t weights[3], 
                                         weights[0].offset, stream );
     return hipSuccess;
 }
-template hipError_t weights_analyse<8>( const WpInput<8> &, x264hip_weight_t *, float *, uint8_t *, hipStream_t );
-template hipError_t weights_analyse<10>( const WpInput<10> &, x264hip_weight_t *, float *, uint16_t *, hipStream_t );
+X264HIP_INSTANTIATE( weights_analyse );
 
 } // namespace x264hip
