@@ -695,8 +695,9 @@ int x264hip_##BD##_frame_integral( const pixel *plane, intptr_t stride, intptr_t
  *     = sad_16x16( fenc_f + 16*(mby*fenc_stride + mbx), fenc_stride,                           \
  *                  ref_f + (16*mby + j - range)*ref_stride + 16*mbx + i - range, ref_stride )   \
  * for 0 <= i,j <= 2*range, i.e. mx = i - range, my = j - range, raster order                   \
- * my-major, row pitch P = (2*range+1 + 3) & ~3 (entries i > 2*range are padding;              \
- * the 8-bit kernel stores the SADs of mx = range+1.. there).  ref must be a                    \
+ * my-major, row pitch P = (2*range+1 + 3) & ~3 (entries i > 2*range are padding:              \
+ * the 8-bit kernel stores zeros there at range 8 and 16, and the SADs of                       \
+ * mx = range+1.. at range 4 and 24).  ref must be a                                            \
  * padded plane (x264 PADH/PADV = 32, reference common/frame.h:32-35); every                    \
  * window row is read from x-range to x+15+range+8, so the caller keeps                        \
  * range+8 <= the horizontal padding (PADH = 32).  range is one of 4, 8, 16, 24. */             \

@@ -195,6 +195,147 @@ __device__ __forceinline__ void me_rows7( const uint32_t *__restrict__ rbase, in
     ( me_row7<R, L, Ys>( rbase, rs_dw, F, acc, sink, e, o ), ... );
 }
 
+// ---------------------------------------------------------------------------
+// Shared last column (un-centred tables, R = 8 / 16): the 2R+1 live columns are 2R / 4 full
+// groups and ONE column, for which the plain kernel runs a whole extra lane per MB (three of
+// its four columns are padding).  Here an MB has only its LM = 2R / 4 qsad lanes, and they
+// share column 2R by fenc row: lane g keeps a second copy of fenc rows g, g + LM, ... (16 / LM
+// rows), takes the 16 ref bytes of window column 2R of every ref row Y from the MB's last lane
+// (its second load holds them; a ds_swizzle broadcast, no memory) and adds the row's partial
+// SADs -- fenc row r against ref row Y belongs to candidate row Y - r -- into the MB's LDS
+// array at slot (Y - r) + 15 with a return-less LDS add.  Y is a compile-time constant, so
+// the slot is an instruction offset on a per-lane base.  Candidate rows outside 0..2R fall
+// into slots 0..14 / 2R+16..2R+30, which nobody reads: no predicate.  Candidate row c is
+// complete after ref row c + 15, the row whose qsads finish it too; the MB's lanes read it
+// back there and store { column 2R, 0, 0, 0 } next to their 8-byte stores, so a table row
+// still leaves one wave within one row step (2.25-2.28 -> 2.17-2.20 ms per 128 1080p pairs,
+// profiles/r08c_colshare_ab.log).
+// An MB never straddles a wave (LM divides 64) and a wave's LDS operations execute in order:
+// zeroing, adding and reading back need no barrier.  A lane's fenc rows are LM apart, so the
+// lanes of an MB hit consecutive banks, and the pitch 64 + LM (= LM mod 32) spreads the MBs of
+// a 32-lane LDS group over all 32 banks: conflict-free.
+template <int R> constexpr int cs_lanes() { return 2 * R / 4; }
+template <int R> constexpr int cs_pitch() { return 64 + cs_lanes<R>(); }
+template <int R> constexpr bool cs_range() { return R == 8 || R == 16; }
+
+template <int R, int L, int Y, class Sink>
+__device__ __forceinline__ void me_row7cs( const uint32_t *__restrict__ rbase, int rs_dw, const uint32_t (&F)[16][4],
+                                           const uint32_t (&FC)[16 / cs_lanes<R>()][4], uint64_t (&acc)[16],
+                                           Sink &sink, u64x2a4 (&e)[L], u64x2a4 (&o)[L], uint32_t *part,
+                                           const uint32_t *sum, uint32_t &col )
+{
+    constexpr int LM = cs_lanes<R>(), NFR = 16 / LM;
+    // lane ((lane & ~(LM - 1)) | (LM - 1))'s value: ds_swizzle bit-mask mode, and | or << 5
+    constexpr int LAST = (0x1f & ~(LM - 1)) | ((LM - 1) << 5);
+    const uint64_t o0 = o[Y % L][0], o1 = o[Y % L][1];
+    const uint32_t w[4] = { (uint32_t)__builtin_amdgcn_ds_swizzle( (int)(uint32_t)o0, LAST ),
+                            (uint32_t)__builtin_amdgcn_ds_swizzle( (int)(uint32_t)(o0 >> 32), LAST ),
+                            (uint32_t)__builtin_amdgcn_ds_swizzle( (int)(uint32_t)o1, LAST ),
+                            (uint32_t)__builtin_amdgcn_ds_swizzle( (int)(uint32_t)(o1 >> 32), LAST ) };
+#pragma unroll
+    for( int j = 0; j < NFR; j++ )
+    {
+        uint32_t s = 0;
+#pragma unroll
+        for( int k = 0; k < 4; k++ )
+            s = __builtin_amdgcn_sad_u8( FC[j][k], w[k], s );
+        // fenc row g + j * LM: slot (Y - g - j * LM) + 15, `part` holds 15 - g - (16 - LM)
+        __hip_atomic_fetch_add( part + Y + LM * (NFR - 1 - j), s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT );
+    }
+    if constexpr( Y >= 15 )
+        col = __hip_atomic_load( sum + Y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT );
+    me_row7<R, L, Y>( rbase, rs_dw, F, acc, sink, e, o );
+}
+
+template <int R, int L, class Sink, int... Ys>
+__device__ __forceinline__ void me_rows7cs( const uint32_t *__restrict__ rbase, int rs_dw, const uint32_t (&F)[16][4],
+                                            const uint32_t (&FC)[16 / cs_lanes<R>()][4], uint64_t (&acc)[16],
+                                            Sink &sink, uint32_t *part, const uint32_t *sum, uint32_t &col,
+                                            std::integer_sequence<int, Ys...> )
+{
+    u64x2a4 e[L], o[L];
+#pragma unroll
+    for( int k = 0; k < L; k++ )
+    {
+        e[k] = *(const u64x2a4 *)(rbase + k * rs_dw);
+        o[k] = *(const u64x2a4 *)(rbase + k * rs_dw + 1);
+    }
+    ( me_row7cs<R, L, Ys>( rbase, rs_dw, F, FC, acc, sink, e, o, part, sum, col ), ... );
+}
+
+template <int R>
+__device__ __forceinline__ void me_full_colshare( const uint8_t *__restrict__ fenc, intptr_t fs, intptr_t ffs,
+                                                  const uint8_t *__restrict__ ref, intptr_t rs, intptr_t rfs, int mbw,
+                                                  int mbh, int nframes, uint16_t *__restrict__ table,
+                                                  int16_t *__restrict__ origin, int xcd )
+{
+    constexpr int P = full_pitch( R ), LM = cs_lanes<R>(), NFR = 16 / LM, LP = cs_pitch<R>();
+    static_assert( 64 % LM == 0 && 16 % LM == 0 && 2 * R + 31 <= LP && LP % LM == 0, "lane / LDS layout" );
+    __shared__ uint32_t colsum[256 / LM * LP];
+    const uint32_t blk = xcd ? xcd_block( blockIdx.x, gridDim.x ) : blockIdx.x;
+    const uint32_t slot = blk * blockDim.x + threadIdx.x;
+    // (whole MBs leave: no live lane shares an LDS array with one that returned)
+    if( slot >= (uint32_t)nframes * (uint32_t)mbh * (uint32_t)mbw * (uint32_t)LM )
+        return;
+    const uint32_t mb32 = slot / LM, t32 = mb32 / (uint32_t)mbw, f32 = t32 / (uint32_t)mbh;
+    const int grp = (int)(slot - mb32 * LM);
+    const int mbx = (int)(mb32 - t32 * (uint32_t)mbw);
+    const int mby = (int)(t32 - f32 * (uint32_t)mbh);
+    const int64_t mb = mb32, f = f32;
+
+    uint32_t *sum = colsum + (threadIdx.x / LM) * LP;
+#pragma unroll
+    for( int k = 0; k < LP / LM; k++ )
+        __hip_atomic_store( sum + grp + k * LM, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT );
+
+    uint32_t F[16][4], FC[NFR][4];
+    const uint32_t *fe = (const uint32_t *)(fenc + f * ffs + (intptr_t)(16 * mby) * fs + 16 * mbx);
+    const int fs_dw = (int)(fs / 4);
+#pragma unroll
+    for( int r = 0; r < 16; r++ )
+#pragma unroll
+        for( int k = 0; k < 4; k++ )
+            F[r][k] = fe[r * fs_dw + k];
+    // the lane's own fenc rows, loaded separately (F cannot be indexed by a lane-varying row)
+#pragma unroll
+    for( int j = 0; j < NFR; j++ )
+#pragma unroll
+        for( int k = 0; k < 4; k++ )
+            FC[j][k] = fe[(grp + j * LM) * fs_dw + k];
+    if( origin && grp == 0 )
+        origin[2 * mb] = origin[2 * mb + 1] = (int16_t)-R;
+    const uint32_t *rbase =
+        (const uint32_t *)(ref + f * rfs + (intptr_t)(16 * mby - R) * rs + 16 * mbx - R + 4 * grp);
+    uint64_t *out = (uint64_t *)(table + mb * ((2 * R + 1) * P) + 4 * grp);
+    // every lane of the MB holds column 2R's sum and every lane stores it (to the same address):
+    // a store predicated on the last lane splits each row into basic blocks, and the compiler
+    // then sinks a candidate row's whole qsad chain to its store, keeping 16 ref rows live
+    // (spills) instead of 16 accumulators
+    uint64_t *outc = out + (LM - grp);
+    uint32_t col = 0;
+    auto store = [out, outc, &col]( int c, uint32_t lo, uint32_t hi ) {
+        out[c * (P / 4)] = ((uint64_t)hi << 32) | lo;
+        outc[c * (P / 4)] = col;
+    };
+    uint64_t acc[16];
+    me_rows7cs<R, ME_LEAD>( rbase, (int)(rs / 4), F, FC, acc, store, sum + 15 - grp - (16 - LM), sum, col,
+                            std::make_integer_sequence<int, 2 * R + 16>{} );
+}
+
+// the kernel's shared-last-column form: LM = G - 1 lanes per MB.  (The extra fenc rows and
+// column dwords take it past 128 VGPRs; held to three waves per SIMD, 168.)
+template <int R, int G, int LM>
+__global__ __launch_bounds__( 256, 3 ) void me_full_sad16_v7_kernel( const uint8_t *__restrict__ fenc, intptr_t fs,
+                                                                     intptr_t ffs, const uint8_t *__restrict__ ref,
+                                                                     intptr_t rs, intptr_t rfs, int mbw, int mbh,
+                                                                     int nframes, uint16_t *__restrict__ table,
+                                                                     const int16_t *__restrict__ centre,
+                                                                     int16_t *__restrict__ origin, int xcd )
+{
+    static_assert( LM == cs_lanes<R>() && G == LM + 1, "un-centred tables only" );
+    me_full_colshare<R>( fenc, fs, ffs, ref, rs, rfs, mbw, mbh, nframes, table, origin, xcd );
+}
+
 // one lane per column group of G (full: align4(2R+1) / 4, centred: cen_pitch / 4)
 template <int R, int G>
 __global__ __launch_bounds__( 256 ) void me_full_sad16_v7_kernel( const uint8_t *__restrict__ fenc, intptr_t fs,
@@ -605,7 +746,9 @@ hipError_t launch_me_full( const typename PT<BD>::pixel *fenc, intptr_t fs, intp
     bool grouped = !(((uintptr_t)fenc | (uintptr_t)ref | (uintptr_t)(fs * PSZ) | (uintptr_t)(rs * PSZ)) & 3);
     if( nmb * groups >= (1ll << 32) )
         grouped = false;                        // (the grouped kernels index their lanes in 32 bits)
-    const int64_t lanes = nmb * (grouped ? groups : ncol);
+    // 8-bit un-centred tables at range 8 / 16: column 2R shared over the full groups' lanes
+    const bool share = grouped && BD == 8 && !cen && (range == 8 || range == 16);
+    const int64_t lanes = nmb * (share ? groups - 1 : grouped ? groups : ncol);
     dim3 blk( 256 ), g( (unsigned)((lanes + 255) / 256) );
     const int xcd = me_xcd();
     switch( range )
@@ -614,6 +757,9 @@ hipError_t launch_me_full( const typename PT<BD>::pixel *fenc, intptr_t fs, intp
     if( !grouped )                                                                                                \
         hipLaunchKernelGGL( ( me_full_sad16_kernel<BD, R, CEN ? cen_pitch( BD, R ) : 2 * R + 1> ), g, blk, 0,    \
                             stream, fenc, fs, ffs, ref, rs, rfs, mbw, mbh, nframes, table, centre, origin );      \
+    else if constexpr( BD == 8 && !CEN && cs_range<R>() )                                                         \
+        hipLaunchKernelGGL( ( me_full_sad16_v7_kernel<R, full_pitch( R ) / 4, cs_lanes<R>()> ), g, blk, 0,        \
+                            stream, fenc, fs, ffs, ref, rs, rfs, mbw, mbh, nframes, table, centre, origin, xcd ); \
     else if constexpr( BD == 8 )                                                                                  \
         hipLaunchKernelGGL( ( me_full_sad16_v7_kernel<R, (CEN ? cen_pitch( 8, R ) : full_pitch( R )) / 4> ), g,   \
                             blk, 0, stream, fenc, fs, ffs, ref, rs, rfs, mbw, mbh, nframes, table, centre, origin, \
