@@ -21,7 +21,11 @@
 //   acc[my] += sad(fenc row (y - my), ref row y)      (v_sad_u8 / v_sad_u16)
 // fenc (16 rows) stays in VGPRs for the whole lane lifetime.  Candidate my finishes at
 // row my+15 and is stored then.  The grouped kernels below (four columns per lane with
-// v_qsad_pk_u16_u8 at 8 bit, column pairs with v_sad_u16 at 10 bit) are the defaults.
+// v_qsad_pk_u16_u8 at 8 bit, column pairs with v_sad_u16 at 10 bit) are the defaults.  They
+// share one row loop, me_walk / me_step, over a ring of loaded ref rows (ring_q, ring_qu,
+// ring_p) and a fold of a row into the open candidate rows (fold_row, fold_lr, fold_pair,
+// fold_quad), with an optional per-row hook (the shared last column), and one prologue
+// (me_lane_of, load_fenc, me_window).
 #include "hipcommon.h"
 #include <mutex>
 #include <string.h>
@@ -70,24 +74,31 @@ __device__ __forceinline__ void me_rows( const typename PT<BD>::pixel *rb, intpt
 // centre = (0, 0)): (cx, cy) - R, clamped so that every pixel a kernel fetches lies in the
 // 32-pixel padded plane (x264's PADH = PADV = 32, common/frame.h:32-33) -- P columns wide,
 // 2R+1 rows -- then aligned down to 4 (8 bit) / 2 (10 bit) pixels so the grouped kernels
-// keep dword-aligned rows.  For centre (0, 0) and R <= 24 neither step changes anything.
+// keep dword-aligned rows (`al`, the alignment mask: 3 / 1; 0 where the kernel realigns its
+// rows itself).  For centre (0, 0) and R <= 24 neither step changes anything.
 // Returned relative to the MB.
+__device__ __forceinline__ void me_window( int R, int P, int al, int cx, int cy, int mbx, int mby, int mbw, int mbh,
+                                           int &ox, int &oy )
+{
+    int ax = 16 * mbx - R + cx, ay = 16 * mby - R + cy;
+    ax = min( max( ax, -32 ), 16 * mbw + 12 - P );
+    ay = min( max( ay, -32 ), 16 * mbh + 16 - 2 * R );
+    ax &= ~al;
+    ox = ax - 16 * mbx;
+    oy = ay - 16 * mby;
+}
+
 template <int BD, int R, int P>
 __device__ __forceinline__ void me_window( const int16_t *__restrict__ centre, int64_t mb, int mbx, int mby, int mbw,
                                            int mbh, int &ox, int &oy )
 {
-    constexpr int AL = BD == 8 ? 4 : 2;
-    int ax = 16 * mbx - R, ay = 16 * mby - R;
+    int cx = 0, cy = 0;
     if( centre )
     {
-        ax += centre[2 * mb];
-        ay += centre[2 * mb + 1];
+        cx = centre[2 * mb];
+        cy = centre[2 * mb + 1];
     }
-    ax = min( max( ax, -32 ), 16 * mbw + 12 - P );
-    ay = min( max( ay, -32 ), 16 * mbh + 16 - 2 * R );
-    ax &= ~(AL - 1);
-    ox = ax - 16 * mbx;
-    oy = ay - 16 * mby;
+    me_window( R, P, BD == 8 ? 3 : 1, cx, cy, mbx, mby, mbw, mbh, ox, oy );
 }
 
 // generic kernel: one lane per table column (NCOL columns, pitch align4(NCOL)); serves
@@ -145,54 +156,304 @@ typedef uint32_t u32x2a4 __attribute__( ( ext_vector_type( 2 ), aligned( 4 ) ) )
 constexpr int ME_LEAD = 2;
 
 // ---------------------------------------------------------------------------
-// 8 bit: one lane owns four adjacent candidate columns 4g..4g+3 and all 16 fenc rows;
-// per ref row it issues two overlapping 16-byte loads (the four 8-byte windows arrive as
-// aligned register pairs, no realignment) and folds the row into the <= 16 candidate rows
-// whose footprint covers it, 16 byte absdiffs per v_qsad_pk_u16_u8 (a column's packed u16
-// sum cannot carry: 16*16*255 < 2^16).  `sink( c, lo, hi )` receives candidate row c's four
-// finished SADs as packed u16 pairs (columns 4g, 4g+1 in lo, 4g+2, 4g+3 in hi).
-template <int R, int L, int Y, class Sink>
-__device__ __forceinline__ void me_row7( const uint32_t *__restrict__ rbase, int rs_dw, const uint32_t (&F)[16][4],
-                                         uint64_t (&acc)[16], Sink &sink, u64x2a4 (&e)[L], u64x2a4 (&o)[L] )
+// The window-row walker: every grouped kernel walks the ref rows Y = 0 .. 2R + NF - 1 of its
+// lane's window (NF = the fenc rows the lane folds, 16 or 8) and folds row Y into the candidate
+// rows c = C0..C1 whose footprint covers it, candidate c against fenc row Y - c.  The kernels
+// differ in two things only:
+//  * the RING of ME_LEAD ref rows in flight -- load( slot, row pointer ) issues a row's loads,
+//    take( slot, windows ) turns a loaded row into the windows the SADs read;
+//  * the FOLD -- fold( c, r, windows ) adds fenc row r's SADs to candidate row c's sums (held
+//    in the fold, slot c % NF), restarts them at the candidate's first row and hands the
+//    finished ones to the kernel's `sink`.
+// me_step is one row: slot Y % L of the ring is consumed, then refilled with row Y + L while
+// there is one.  An optional hook runs first, with Y as a compile-time constant and the ring
+// (the shared last column below).
+struct me_no_hook
 {
-    constexpr int C0 = Y - 15 > 0 ? Y - 15 : 0;
+    template <class Y, class Ring> __device__ __forceinline__ void operator()( Y, Ring & ) const {}
+};
+
+template <int R, int NF, int L, int Y, class Ring, class Fold, class Hook>
+__device__ __forceinline__ void me_step( const uint32_t *__restrict__ rbase, int rs_dw, Ring &ring, Fold &fold,
+                                         Hook &hook )
+{
+    constexpr int C0 = Y - (NF - 1) > 0 ? Y - (NF - 1) : 0;
     constexpr int C1 = Y < 2 * R ? Y : 2 * R;
-    const uint64_t win[4] = { e[Y % L][0], o[Y % L][0], e[Y % L][1], o[Y % L][1] };
-    if constexpr( Y + L < 2 * R + 16 )
-    {
-        const uint32_t *row = rbase + (Y + L) * rs_dw;
-        e[Y % L] = *(const u64x2a4 *)row;
-        o[Y % L] = *(const u64x2a4 *)(row + 1);
-    }
+    hook( std::integral_constant<int, Y>{}, ring );
+    typename Ring::windows w;
+    ring.take( Y % L, w );
+    if constexpr( Y + L < 2 * R + NF )
+        ring.load( Y % L, rbase + (Y + L) * rs_dw );
 #pragma unroll
     for( int c = C0; c <= C1; c++ )
+        fold( c, Y - c, w );
+    // keep the scheduler from hoisting later rows' loads up here
+    __builtin_amdgcn_sched_barrier( 0 );
+}
+
+template <int R, int NF, int L, class Ring, class Fold, class Hook, int... Ys>
+__device__ __forceinline__ void me_walk( const uint32_t *__restrict__ rbase, int rs_dw, Ring &ring, Fold &fold,
+                                         Hook &hook, std::integer_sequence<int, Ys...> )
+{
+#pragma unroll
+    for( int k = 0; k < L; k++ )
+        ring.load( k, rbase + k * rs_dw );
+    ( me_step<R, NF, L, Ys>( rbase, rs_dw, ring, fold, hook ), ... );
+}
+
+template <int R, int NF, int L, class Ring, class Fold, class Hook = me_no_hook>
+__device__ __forceinline__ void me_walk( const uint32_t *__restrict__ rbase, int rs_dw, Ring &ring, Fold &fold,
+                                         Hook hook = {} )
+{
+    me_walk<R, NF, L>( rbase, rs_dw, ring, fold, hook, std::make_integer_sequence<int, 2 * R + NF>{} );
+}
+
+// 8 bit: one lane owns four adjacent candidate columns 4g..4g+3; a row's windows are the four
+// 8-byte windows of those columns, 16 byte absdiffs per v_qsad_pk_u16_u8 against a fenc dword.
+struct win_q
+{
+    uint64_t w[4];
+};
+
+// dword-aligned windows: two overlapping 16-byte loads per row (the four windows arrive as
+// aligned register pairs, no realignment)
+template <int L> struct ring_q
+{
+    typedef win_q windows;
+    u64x2a4 e[L], o[L];
+    __device__ __forceinline__ void load( int k, const uint32_t *row )
     {
-        const int r = Y - c;
+        e[k] = *(const u64x2a4 *)row;
+        o[k] = *(const u64x2a4 *)(row + 1);
+    }
+    __device__ __forceinline__ void take( int k, win_q &w ) const
+    {
+        w.w[0] = e[k][0];
+        w.w[1] = o[k][0];
+        w.w[2] = e[k][1];
+        w.w[3] = o[k][1];
+    }
+};
+
+// windows at any byte offset: the row pointer is the dword holding the lane's first window
+// byte, sh that byte's offset in it.  Each row is six aligned dwords (the 20 bytes the lane's
+// windows span, at any offset) realigned with v_alignbyte: a misaligned 16-byte load costs the
+// address path 4x an aligned one (profiles/r01d_ta_probe.txt), which made the esa8 template
+// pass address-bound off the dword grid.
+template <int L> struct ring_qu
+{
+    typedef win_q windows;
+    u32x4a4 wl[L];
+    u32x2a4 wh[L];
+    uint32_t sh;
+    __device__ __forceinline__ void load( int k, const uint32_t *row )
+    {
+        wl[k] = *(const u32x4a4 *)row;
+        wh[k] = *(const u32x2a4 *)(row + 4);
+    }
+    __device__ __forceinline__ void take( int k, win_q &w ) const
+    {
+        const u32x4a4 l4 = wl[k];
+        const u32x2a4 h2 = wh[k];
+        const uint32_t d0 = __builtin_amdgcn_alignbyte( l4.y, l4.x, sh ), d1 = __builtin_amdgcn_alignbyte( l4.z, l4.y, sh );
+        const uint32_t d2 = __builtin_amdgcn_alignbyte( l4.w, l4.z, sh ), d3 = __builtin_amdgcn_alignbyte( h2.x, l4.w, sh );
+        const uint32_t d4 = __builtin_amdgcn_alignbyte( h2.y, h2.x, sh );
+        w.w[0] = (uint64_t)d1 << 32 | d0;
+        w.w[1] = (uint64_t)d2 << 32 | d1;
+        w.w[2] = (uint64_t)d3 << 32 | d2;
+        w.w[3] = (uint64_t)d4 << 32 | d3;
+    }
+};
+
+// 10 bit: a lane owns two adjacent candidate columns (2g, 2g+1; the first is dword aligned
+// for even R) and half of the fenc rows (lane pair h = 0/1: rows 8h..8h+7); per ref row it
+// loads 9 dwords once and forms the odd column's dwords with one v_alignbyte_b32 each.
+struct win_p
+{
+    uint32_t w[9], o[8];
+};
+
+template <int L> struct ring_p
+{
+    typedef win_p windows;
+    uint32_t d[L][9];
+    __device__ __forceinline__ void load( int k, const uint32_t *row )
+    {
+#pragma unroll
+        for( int j = 0; j < 9; j++ )
+            d[k][j] = row[j];
+    }
+    __device__ __forceinline__ void take( int k, win_p &w ) const
+    {
+#pragma unroll
+        for( int j = 0; j < 9; j++ )
+            w.w[j] = d[k][j];
+#pragma unroll
+        for( int j = 0; j < 8; j++ )
+            w.o[j] = __builtin_amdgcn_alignbyte( w.w[j + 1], w.w[j], 2 );
+    }
+};
+
+// 8 bit, whole rows: all 16 fenc rows, the four columns' sums packed in one uint64_t (a
+// column's packed u16 sum cannot carry: 16*16*255 < 2^16).  `sink( c, lo, hi )` receives
+// candidate row c's four finished SADs as packed u16 pairs (columns 4g, 4g+1 in lo, 4g+2,
+// 4g+3 in hi).
+template <class Sink> struct fold_row
+{
+    const uint32_t ( &F )[16][4];
+    Sink &sink;
+    uint64_t acc[16];
+    __device__ __forceinline__ fold_row( const uint32_t ( &F )[16][4], Sink &sink ) : F( F ), sink( sink ) {}
+    __device__ __forceinline__ void operator()( int c, int r, const win_q &w )
+    {
         uint64_t a = r == 0 ? 0ull : acc[c & 15];
 #pragma unroll
         for( int k = 0; k < 4; k++ )
-            a = __builtin_amdgcn_qsad_pk_u16_u8( win[k], F[r][k], a );
+            a = __builtin_amdgcn_qsad_pk_u16_u8( w.w[k], F[r][k], a );
         if( r == 15 )
             sink( c, (uint32_t)a, (uint32_t)(a >> 32) );
         else
             acc[c & 15] = a;
     }
-    // keep the scheduler from hoisting later rows' loads up here
-    __builtin_amdgcn_sched_barrier( 0 );
+};
+
+// 8 bit, 8x8 quadrants: separate left (fenc dwords 0-1) and right (dwords 2-3) sums, restarted
+// every eight fenc rows.  With NF = 16 a candidate row's top quadrants leave at fenc row 7 and
+// its bottom ones at row 15 (the same 256 absdiffs per candidate as the 16x16 table, whose SAD
+// is the sum of the four; 16x8 / 8x16 SADs are pair sums); with NF = 8 the lane folds one half
+// of the MB.  `sink( c, half, a, b )`: the left and right quadrants of fenc rows 8 half .. + 7.
+template <int NF, class Sink> struct fold_lr
+{
+    const uint32_t ( &F )[NF][4];
+    Sink &sink;
+    uint64_t al[NF], ar[NF];
+    __device__ __forceinline__ fold_lr( const uint32_t ( &F )[NF][4], Sink &sink ) : F( F ), sink( sink ) {}
+    __device__ __forceinline__ void operator()( int c, int r, const win_q &w )
+    {
+        uint64_t a = (r & 7) == 0 ? 0ull : al[c & (NF - 1)], b = (r & 7) == 0 ? 0ull : ar[c & (NF - 1)];
+        a = __builtin_amdgcn_qsad_pk_u16_u8( w.w[0], F[r][0], a );
+        a = __builtin_amdgcn_qsad_pk_u16_u8( w.w[1], F[r][1], a );
+        b = __builtin_amdgcn_qsad_pk_u16_u8( w.w[2], F[r][2], b );
+        b = __builtin_amdgcn_qsad_pk_u16_u8( w.w[3], F[r][3], b );
+        if( (r & 7) == 7 )
+            sink( c, r >> 3, a, b );
+        else
+        {
+            al[c & (NF - 1)] = a;
+            ar[c & (NF - 1)] = b;
+        }
+    }
+};
+
+// 10 bit, column pair: the lane's eight fenc rows against both columns with v_sad_u16.
+// `sink( c, a0, a1 )` receives candidate row c's two finished SADs (columns 2g, 2g+1),
+// identical in both lanes of the pair after the DPP add.
+template <class Sink> struct fold_pair
+{
+    const uint32_t ( &F )[8][8];
+    Sink &sink;
+    uint32_t acc[8][2];
+    __device__ __forceinline__ fold_pair( const uint32_t ( &F )[8][8], Sink &sink ) : F( F ), sink( sink ) {}
+    __device__ __forceinline__ void operator()( int c, int r, const win_p &w )
+    {
+        uint32_t a0 = r == 0 ? 0u : acc[c & 7][0], a1 = r == 0 ? 0u : acc[c & 7][1];
+#pragma unroll
+        for( int k = 0; k < 8; k++ )
+        {
+            a0 = __builtin_amdgcn_sad_u16( F[r][k], w.w[k], a0 );
+            a1 = __builtin_amdgcn_sad_u16( F[r][k], w.o[k], a1 );
+        }
+        if( r == 7 )
+        {
+            a0 += (uint32_t)__builtin_amdgcn_update_dpp( 0, (int)a0, 0xB1, 0xF, 0xF, false );
+            a1 += (uint32_t)__builtin_amdgcn_update_dpp( 0, (int)a1, 0xB1, 0xF, 0xF, false );
+            sink( c, a0, a1 );
+        }
+        else
+        {
+            acc[c & 7][0] = a0;
+            acc[c & 7][1] = a1;
+        }
+    }
+};
+
+// 10 bit, 8x8 quadrants: the column-pair lane, whose fenc row half h is already a quadrant row
+// (h = 0 top, 1 bottom); the 8 dwords of a fenc row split into left (dwords 0-3) and right
+// (4-7) sums, so a lane's candidate row leaves as four 8x8 SADs (two columns x left / right)
+// at fenc row 7 without the pair's DPP add: `sink( c, left, right )`, columns 2g, 2g+1 packed
+// as u16.  An 8x8 SAD at 10 bit is at most 64 * 1023 = 65472: the quadrant tables stay uint16.
+template <class Sink> struct fold_quad
+{
+    const uint32_t ( &F )[8][8];
+    Sink &sink;
+    uint32_t acc[8][4];
+    __device__ __forceinline__ fold_quad( const uint32_t ( &F )[8][8], Sink &sink ) : F( F ), sink( sink ) {}
+    __device__ __forceinline__ void operator()( int c, int r, const win_p &w )
+    {
+        uint32_t a[4];
+#pragma unroll
+        for( int j = 0; j < 4; j++ )
+            a[j] = r == 0 ? 0u : acc[c & 7][j];
+#pragma unroll
+        for( int k = 0; k < 4; k++ )
+        {
+            a[0] = __builtin_amdgcn_sad_u16( F[r][k], w.w[k], a[0] );              // column 2g, left
+            a[1] = __builtin_amdgcn_sad_u16( F[r][k], w.o[k], a[1] );              // column 2g+1, left
+            a[2] = __builtin_amdgcn_sad_u16( F[r][k + 4], w.w[k + 4], a[2] );      // column 2g, right
+            a[3] = __builtin_amdgcn_sad_u16( F[r][k + 4], w.o[k + 4], a[3] );      // column 2g+1, right
+        }
+        if( r == 7 )
+            sink( c, a[0] | (a[1] << 16), a[2] | (a[3] << 16) );
+        else
+        {
+#pragma unroll
+            for( int j = 0; j < 4; j++ )
+                acc[c & 7][j] = a[j];
+        }
+    }
+};
+
+// ---------------------------------------------------------------------------
+// The prologue every walking kernel opens with.
+// fenc rows stay resident in registers: NR rows of NDW dwords from fe, rows fs_dw dwords apart
+template <int NR, int NDW>
+__device__ __forceinline__ void load_fenc( uint32_t ( &F )[NR][NDW], const uint32_t *fe, int fs_dw )
+{
+#pragma unroll
+    for( int r = 0; r < NR; r++ )
+#pragma unroll
+        for( int k = 0; k < NDW; k++ )
+            F[r][k] = fe[r * fs_dw + k];
 }
 
-template <int R, int L, class Sink, int... Ys>
-__device__ __forceinline__ void me_rows7( const uint32_t *__restrict__ rbase, int rs_dw, const uint32_t (&F)[16][4],
-                                          uint64_t (&acc)[16], Sink &sink, std::integer_sequence<int, Ys...> )
+// A table kernel's lane: LPM lanes per MB over the nframes * mbh * mbw MBs.  The lane is column
+// group `grp` of MB `mb` = (frame f, mbx, mby); with PAIR (10 bit) the lanes are pairs h = 0 / 1
+// of LPM / 2 groups.
+// 32-bit index decomposition (the launcher keeps the lane count below 2^32): the
+// int64 divisions by mbw / mbh were ~150 VALU instructions of the prologue
+struct me_lane
 {
-    u64x2a4 e[L], o[L];
-#pragma unroll
-    for( int k = 0; k < L; k++ )
-    {
-        e[k] = *(const u64x2a4 *)(rbase + k * rs_dw);
-        o[k] = *(const u64x2a4 *)(rbase + k * rs_dw + 1);
-    }
-    ( me_row7<R, L, Ys>( rbase, rs_dw, F, acc, sink, e, o ), ... );
+    int64_t mb, f;
+    int mbx, mby, grp, h;
+    bool live;
+};
+template <int LPM, bool PAIR>
+__device__ __forceinline__ me_lane me_lane_of( int xcd, int nframes, int mbh, int mbw )
+{
+    const uint32_t blk = xcd ? xcd_block( blockIdx.x, gridDim.x ) : blockIdx.x;
+    const uint32_t slot = blk * blockDim.x + threadIdx.x;
+    me_lane l = {};
+    l.live = slot < (uint32_t)nframes * (uint32_t)mbh * (uint32_t)mbw * (uint32_t)LPM;
+    if( !l.live )
+        return l;
+    const uint32_t mb32 = slot / LPM, t32 = mb32 / (uint32_t)mbw, f32 = t32 / (uint32_t)mbh;
+    l.h = PAIR ? (int)(slot & 1) : 0;
+    l.grp = PAIR ? (int)((slot >> 1) - mb32 * (LPM / 2)) : (int)(slot - mb32 * LPM);
+    l.mbx = (int)(mb32 - t32 * (uint32_t)mbw);
+    l.mby = (int)(t32 - f32 * (uint32_t)mbh);
+    l.mb = mb32;
+    l.f = f32;
+    return l;
 }
 
 // ---------------------------------------------------------------------------
@@ -218,51 +479,6 @@ template <int R> constexpr int cs_lanes() { return 2 * R / 4; }
 template <int R> constexpr int cs_pitch() { return 64 + cs_lanes<R>(); }
 template <int R> constexpr bool cs_range() { return R == 8 || R == 16; }
 
-template <int R, int L, int Y, class Sink>
-__device__ __forceinline__ void me_row7cs( const uint32_t *__restrict__ rbase, int rs_dw, const uint32_t (&F)[16][4],
-                                           const uint32_t (&FC)[16 / cs_lanes<R>()][4], uint64_t (&acc)[16],
-                                           Sink &sink, u64x2a4 (&e)[L], u64x2a4 (&o)[L], uint32_t *part,
-                                           const uint32_t *sum, uint32_t &col )
-{
-    constexpr int LM = cs_lanes<R>(), NFR = 16 / LM;
-    // lane ((lane & ~(LM - 1)) | (LM - 1))'s value: ds_swizzle bit-mask mode, and | or << 5
-    constexpr int LAST = (0x1f & ~(LM - 1)) | ((LM - 1) << 5);
-    const uint64_t o0 = o[Y % L][0], o1 = o[Y % L][1];
-    const uint32_t w[4] = { (uint32_t)__builtin_amdgcn_ds_swizzle( (int)(uint32_t)o0, LAST ),
-                            (uint32_t)__builtin_amdgcn_ds_swizzle( (int)(uint32_t)(o0 >> 32), LAST ),
-                            (uint32_t)__builtin_amdgcn_ds_swizzle( (int)(uint32_t)o1, LAST ),
-                            (uint32_t)__builtin_amdgcn_ds_swizzle( (int)(uint32_t)(o1 >> 32), LAST ) };
-#pragma unroll
-    for( int j = 0; j < NFR; j++ )
-    {
-        uint32_t s = 0;
-#pragma unroll
-        for( int k = 0; k < 4; k++ )
-            s = __builtin_amdgcn_sad_u8( FC[j][k], w[k], s );
-        // fenc row g + j * LM: slot (Y - g - j * LM) + 15, `part` holds 15 - g - (16 - LM)
-        __hip_atomic_fetch_add( part + Y + LM * (NFR - 1 - j), s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT );
-    }
-    if constexpr( Y >= 15 )
-        col = __hip_atomic_load( sum + Y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT );
-    me_row7<R, L, Y>( rbase, rs_dw, F, acc, sink, e, o );
-}
-
-template <int R, int L, class Sink, int... Ys>
-__device__ __forceinline__ void me_rows7cs( const uint32_t *__restrict__ rbase, int rs_dw, const uint32_t (&F)[16][4],
-                                            const uint32_t (&FC)[16 / cs_lanes<R>()][4], uint64_t (&acc)[16],
-                                            Sink &sink, uint32_t *part, const uint32_t *sum, uint32_t &col,
-                                            std::integer_sequence<int, Ys...> )
-{
-    u64x2a4 e[L], o[L];
-#pragma unroll
-    for( int k = 0; k < L; k++ )
-    {
-        e[k] = *(const u64x2a4 *)(rbase + k * rs_dw);
-        o[k] = *(const u64x2a4 *)(rbase + k * rs_dw + 1);
-    }
-    ( me_row7cs<R, L, Ys>( rbase, rs_dw, F, FC, acc, sink, e, o, part, sum, col ), ... );
-}
-
 template <int R>
 __device__ __forceinline__ void me_full_colshare( const uint8_t *__restrict__ fenc, intptr_t fs, intptr_t ffs,
                                                   const uint8_t *__restrict__ ref, intptr_t rs, intptr_t rfs, int mbw,
@@ -272,16 +488,11 @@ __device__ __forceinline__ void me_full_colshare( const uint8_t *__restrict__ fe
     constexpr int P = full_pitch( R ), LM = cs_lanes<R>(), NFR = 16 / LM, LP = cs_pitch<R>();
     static_assert( 64 % LM == 0 && 16 % LM == 0 && 2 * R + 31 <= LP && LP % LM == 0, "lane / LDS layout" );
     __shared__ uint32_t colsum[256 / LM * LP];
-    const uint32_t blk = xcd ? xcd_block( blockIdx.x, gridDim.x ) : blockIdx.x;
-    const uint32_t slot = blk * blockDim.x + threadIdx.x;
+    const me_lane l = me_lane_of<LM, false>( xcd, nframes, mbh, mbw );
     // (whole MBs leave: no live lane shares an LDS array with one that returned)
-    if( slot >= (uint32_t)nframes * (uint32_t)mbh * (uint32_t)mbw * (uint32_t)LM )
+    if( !l.live )
         return;
-    const uint32_t mb32 = slot / LM, t32 = mb32 / (uint32_t)mbw, f32 = t32 / (uint32_t)mbh;
-    const int grp = (int)(slot - mb32 * LM);
-    const int mbx = (int)(mb32 - t32 * (uint32_t)mbw);
-    const int mby = (int)(t32 - f32 * (uint32_t)mbh);
-    const int64_t mb = mb32, f = f32;
+    const int grp = l.grp;
 
     uint32_t *sum = colsum + (threadIdx.x / LM) * LP;
 #pragma unroll
@@ -289,24 +500,17 @@ __device__ __forceinline__ void me_full_colshare( const uint8_t *__restrict__ fe
         __hip_atomic_store( sum + grp + k * LM, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT );
 
     uint32_t F[16][4], FC[NFR][4];
-    const uint32_t *fe = (const uint32_t *)(fenc + f * ffs + (intptr_t)(16 * mby) * fs + 16 * mbx);
+    const uint32_t *fe = (const uint32_t *)(fenc + l.f * ffs + (intptr_t)(16 * l.mby) * fs + 16 * l.mbx);
     const int fs_dw = (int)(fs / 4);
-#pragma unroll
-    for( int r = 0; r < 16; r++ )
-#pragma unroll
-        for( int k = 0; k < 4; k++ )
-            F[r][k] = fe[r * fs_dw + k];
-    // the lane's own fenc rows, loaded separately (F cannot be indexed by a lane-varying row)
-#pragma unroll
-    for( int j = 0; j < NFR; j++ )
-#pragma unroll
-        for( int k = 0; k < 4; k++ )
-            FC[j][k] = fe[(grp + j * LM) * fs_dw + k];
+    load_fenc( F, fe, fs_dw );
+    // the lane's own fenc rows g, g + LM, ..., loaded separately (F cannot be indexed by a
+    // lane-varying row)
+    load_fenc( FC, fe + grp * fs_dw, LM * fs_dw );
     if( origin && grp == 0 )
-        origin[2 * mb] = origin[2 * mb + 1] = (int16_t)-R;
+        origin[2 * l.mb] = origin[2 * l.mb + 1] = (int16_t)-R;
     const uint32_t *rbase =
-        (const uint32_t *)(ref + f * rfs + (intptr_t)(16 * mby - R) * rs + 16 * mbx - R + 4 * grp);
-    uint64_t *out = (uint64_t *)(table + mb * ((2 * R + 1) * P) + 4 * grp);
+        (const uint32_t *)(ref + l.f * rfs + (intptr_t)(16 * l.mby - R) * rs + 16 * l.mbx - R + 4 * grp);
+    uint64_t *out = (uint64_t *)(table + l.mb * ((2 * R + 1) * P) + 4 * grp);
     // every lane of the MB holds column 2R's sum and every lane stores it (to the same address):
     // a store predicated on the last lane splits each row into basic blocks, and the compiler
     // then sinks a candidate row's whole qsad chain to its store, keeping 16 ref rows live
@@ -317,9 +521,34 @@ __device__ __forceinline__ void me_full_colshare( const uint8_t *__restrict__ fe
         out[c * (P / 4)] = ((uint64_t)hi << 32) | lo;
         outc[c * (P / 4)] = col;
     };
-    uint64_t acc[16];
-    me_rows7cs<R, ME_LEAD>( rbase, (int)(rs / 4), F, FC, acc, store, sum + 15 - grp - (16 - LM), sum, col,
-                            std::make_integer_sequence<int, 2 * R + 16>{} );
+    // the row hook: column 2R's 16 ref bytes of row Y from the MB's last lane, the partial SADs
+    // of the lane's fenc rows into LDS, and the finished sum of candidate row Y - 15 read back
+    // lane ((lane & ~(LM - 1)) | (LM - 1))'s value: ds_swizzle bit-mask mode, and | or << 5
+    constexpr int LAST = (0x1f & ~(LM - 1)) | ((LM - 1) << 5);
+    // fenc row g + j * LM: slot (Y - g - j * LM) + 15, `part` holds 15 - g - (16 - LM)
+    uint32_t *part = sum + 15 - grp - (16 - LM);
+    auto column = [&]( auto y, const ring_q<ME_LEAD> &ring ) __attribute__( ( always_inline ) ) {
+        constexpr int Y = decltype( y )::value;
+        const uint64_t o0 = ring.o[Y % ME_LEAD][0], o1 = ring.o[Y % ME_LEAD][1];
+        const uint32_t w[4] = { (uint32_t)__builtin_amdgcn_ds_swizzle( (int)(uint32_t)o0, LAST ),
+                                (uint32_t)__builtin_amdgcn_ds_swizzle( (int)(uint32_t)(o0 >> 32), LAST ),
+                                (uint32_t)__builtin_amdgcn_ds_swizzle( (int)(uint32_t)o1, LAST ),
+                                (uint32_t)__builtin_amdgcn_ds_swizzle( (int)(uint32_t)(o1 >> 32), LAST ) };
+#pragma unroll
+        for( int j = 0; j < NFR; j++ )
+        {
+            uint32_t s = 0;
+#pragma unroll
+            for( int k = 0; k < 4; k++ )
+                s = __builtin_amdgcn_sad_u8( FC[j][k], w[k], s );
+            __hip_atomic_fetch_add( part + Y + LM * (NFR - 1 - j), s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT );
+        }
+        if constexpr( Y >= 15 )
+            col = __hip_atomic_load( sum + Y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT );
+    };
+    ring_q<ME_LEAD> ring;
+    fold_row fold( F, store );
+    me_walk<R, 16, ME_LEAD>( rbase, (int)(rs / 4), ring, fold, column );
 }
 
 // the kernel's shared-last-column form: LM = G - 1 lanes per MB.  (The extra fenc rows and
@@ -346,39 +575,26 @@ __global__ __launch_bounds__( 256 ) void me_full_sad16_v7_kernel( const uint8_t 
                                                                   int16_t *__restrict__ origin, int xcd )
 {
     constexpr int P = 4 * G;                    // table row pitch
-    // 32-bit index decomposition (the launcher keeps the lane count below 2^32): the
-    // int64 divisions by mbw / mbh were ~150 VALU instructions of the prologue
-    const uint32_t blk = xcd ? xcd_block( blockIdx.x, gridDim.x ) : blockIdx.x;
-    const uint32_t slot = blk * blockDim.x + threadIdx.x;
-    if( slot >= (uint32_t)nframes * (uint32_t)mbh * (uint32_t)mbw * (uint32_t)G )
+    const me_lane l = me_lane_of<G, false>( xcd, nframes, mbh, mbw );
+    if( !l.live )
         return;
-    const uint32_t mb32 = slot / G, t32 = mb32 / (uint32_t)mbw, f32 = t32 / (uint32_t)mbh;
-    const int grp = (int)(slot - mb32 * G);
-    const int mbx = (int)(mb32 - t32 * (uint32_t)mbw);
-    const int mby = (int)(t32 - f32 * (uint32_t)mbh);
-    const int64_t mb = mb32, f = f32;
 
     uint32_t F[16][4];
-    const uint32_t *fe = (const uint32_t *)(fenc + f * ffs + (intptr_t)(16 * mby) * fs + 16 * mbx);
-    const int fs_dw = (int)(fs / 4);
-#pragma unroll
-    for( int r = 0; r < 16; r++ )
-#pragma unroll
-        for( int k = 0; k < 4; k++ )
-            F[r][k] = fe[r * fs_dw + k];
+    load_fenc( F, (const uint32_t *)(fenc + l.f * ffs + (intptr_t)(16 * l.mby) * fs + 16 * l.mbx), (int)(fs / 4) );
     int ox, oy;
-    me_window<8, R, P>( centre, mb, mbx, mby, mbw, mbh, ox, oy );
-    if( origin && grp == 0 )
+    me_window<8, R, P>( centre, l.mb, l.mbx, l.mby, mbw, mbh, ox, oy );
+    if( origin && l.grp == 0 )
     {
-        origin[2 * mb] = (int16_t)ox;
-        origin[2 * mb + 1] = (int16_t)oy;
+        origin[2 * l.mb] = (int16_t)ox;
+        origin[2 * l.mb + 1] = (int16_t)oy;
     }
     const uint32_t *rbase =
-        (const uint32_t *)(ref + f * rfs + (intptr_t)(16 * mby + oy) * rs + 16 * mbx + ox + 4 * grp);
-    uint64_t *out = (uint64_t *)(table + mb * ((2 * R + 1) * P) + 4 * grp);
+        (const uint32_t *)(ref + l.f * rfs + (intptr_t)(16 * l.mby + oy) * rs + 16 * l.mbx + ox + 4 * l.grp);
+    uint64_t *out = (uint64_t *)(table + l.mb * ((2 * R + 1) * P) + 4 * l.grp);
     auto store = [out]( int c, uint32_t lo, uint32_t hi ) { out[c * (P / 4)] = ((uint64_t)hi << 32) | lo; };
-    uint64_t acc[16];
-    me_rows7<R, ME_LEAD>( rbase, (int)(rs / 4), F, acc, store, std::make_integer_sequence<int, 2 * R + 16>{} );
+    ring_q<ME_LEAD> ring;
+    fold_row fold( F, store );
+    me_walk<R, 16, ME_LEAD>( rbase, (int)(rs / 4), ring, fold );
 }
 
 // ---------------------------------------------------------------------------
@@ -387,60 +603,7 @@ __global__ __launch_bounds__( 256 ) void me_full_sad16_v7_kernel( const uint8_t 
 // one XCD's L2 (FETCH_SIZE 160 -> 69 MB per 16 1080p pairs, profiles/r03c_*)
 static int me_xcd() { return variant( V_ME_XCD ) != 0; }
 
-// 8x8 quadrant tables (8 bit): the four-column lane with separate left (fenc dwords 0-1)
-// and right (dwords 2-3) accumulators, restarted at fenc row 8: a candidate row's top
-// quadrants leave at fenc row 7, its bottom ones at row 15.  The same 256 absdiffs per
-// candidate as the 16x16 table -- whose SAD is the sum of the four -- and 16x8 / 8x16
-// SADs are pair sums.
-template <int R, int L, int Y, class Sink>
-__device__ __forceinline__ void me_row8q( const uint32_t *__restrict__ rbase, int rs_dw, const uint32_t (&F)[16][4],
-                                          uint64_t (&al)[16], uint64_t (&ar)[16], Sink &sink, u64x2a4 (&e)[L],
-                                          u64x2a4 (&o)[L] )
-{
-    constexpr int C0 = Y - 15 > 0 ? Y - 15 : 0;
-    constexpr int C1 = Y < 2 * R ? Y : 2 * R;
-    const uint64_t win[4] = { e[Y % L][0], o[Y % L][0], e[Y % L][1], o[Y % L][1] };
-    if constexpr( Y + L < 2 * R + 16 )
-    {
-        const uint32_t *row = rbase + (Y + L) * rs_dw;
-        e[Y % L] = *(const u64x2a4 *)row;
-        o[Y % L] = *(const u64x2a4 *)(row + 1);
-    }
-#pragma unroll
-    for( int c = C0; c <= C1; c++ )
-    {
-        const int r = Y - c;
-        uint64_t a = (r & 7) == 0 ? 0ull : al[c & 15], b = (r & 7) == 0 ? 0ull : ar[c & 15];
-        a = __builtin_amdgcn_qsad_pk_u16_u8( win[0], F[r][0], a );
-        a = __builtin_amdgcn_qsad_pk_u16_u8( win[1], F[r][1], a );
-        b = __builtin_amdgcn_qsad_pk_u16_u8( win[2], F[r][2], b );
-        b = __builtin_amdgcn_qsad_pk_u16_u8( win[3], F[r][3], b );
-        if( (r & 7) == 7 )
-            sink( c, r >> 3, a, b );
-        else
-        {
-            al[c & 15] = a;
-            ar[c & 15] = b;
-        }
-    }
-    __builtin_amdgcn_sched_barrier( 0 );
-}
-
-template <int R, int L, class Sink, int... Ys>
-__device__ __forceinline__ void me_rows8q( const uint32_t *__restrict__ rbase, int rs_dw, const uint32_t (&F)[16][4],
-                                           uint64_t (&al)[16], uint64_t (&ar)[16], Sink &sink,
-                                           std::integer_sequence<int, Ys...> )
-{
-    u64x2a4 e[L], o[L];
-#pragma unroll
-    for( int k = 0; k < L; k++ )
-    {
-        e[k] = *(const u64x2a4 *)(rbase + k * rs_dw);
-        o[k] = *(const u64x2a4 *)(rbase + k * rs_dw + 1);
-    }
-    ( me_row8q<R, L, Ys>( rbase, rs_dw, F, al, ar, sink, e, o ), ... );
-}
-
+// 8x8 quadrant tables (8 bit): the four-column lane with fold_lr
 // table8[mb][q][2R+1][P]: q = 0 top-left, 1 top-right, 2 bottom-left, 3 bottom-right
 template <int R>
 __global__ __launch_bounds__( 256 ) void me_full_sad8q_kernel( const uint8_t *__restrict__ fenc, intptr_t fs,
@@ -449,99 +612,25 @@ __global__ __launch_bounds__( 256 ) void me_full_sad8q_kernel( const uint8_t *__
                                                                int nframes, uint16_t *__restrict__ table8, int xcd )
 {
     constexpr int P = full_pitch( R ), G = P / 4;
-    const uint32_t blk = xcd ? xcd_block( blockIdx.x, gridDim.x ) : blockIdx.x;
-    const uint32_t slot = blk * blockDim.x + threadIdx.x;
-    if( slot >= (uint32_t)nframes * (uint32_t)mbh * (uint32_t)mbw * (uint32_t)G )
+    const me_lane l = me_lane_of<G, false>( xcd, nframes, mbh, mbw );
+    if( !l.live )
         return;
-    const uint32_t mb32 = slot / G, t32 = mb32 / (uint32_t)mbw, f32 = t32 / (uint32_t)mbh;
-    const int grp = (int)(slot - mb32 * G);
-    const int mbx = (int)(mb32 - t32 * (uint32_t)mbw);
-    const int mby = (int)(t32 - f32 * (uint32_t)mbh);
-    const int64_t mb = mb32, f = f32;
     uint32_t F[16][4];
-    const uint32_t *fe = (const uint32_t *)(fenc + f * ffs + (intptr_t)(16 * mby) * fs + 16 * mbx);
-    const int fs_dw = (int)(fs / 4);
-#pragma unroll
-    for( int r = 0; r < 16; r++ )
-#pragma unroll
-        for( int k = 0; k < 4; k++ )
-            F[r][k] = fe[r * fs_dw + k];
-    const uint32_t *rbase = (const uint32_t *)(ref + f * rfs + (intptr_t)(16 * mby - R) * rs + 16 * mbx - R + 4 * grp);
-    uint64_t *out = (uint64_t *)(table8 + mb * (4 * (2 * R + 1) * P) + 4 * grp);
+    load_fenc( F, (const uint32_t *)(fenc + l.f * ffs + (intptr_t)(16 * l.mby) * fs + 16 * l.mbx), (int)(fs / 4) );
+    const uint32_t *rbase =
+        (const uint32_t *)(ref + l.f * rfs + (intptr_t)(16 * l.mby - R) * rs + 16 * l.mbx - R + 4 * l.grp);
+    uint64_t *out = (uint64_t *)(table8 + l.mb * (4 * (2 * R + 1) * P) + 4 * l.grp);
     auto store = [out]( int c, int half, uint64_t a, uint64_t b ) {
         out[((2 * half) * (2 * R + 1) + c) * (P / 4)] = a;
         out[((2 * half + 1) * (2 * R + 1) + c) * (P / 4)] = b;
     };
-    uint64_t al[16], ar[16];
-    me_rows8q<R, ME_LEAD>( rbase, (int)(rs / 4), F, al, ar, store, std::make_integer_sequence<int, 2 * R + 16>{} );
+    ring_q<ME_LEAD> ring;
+    fold_lr fold( F, store );
+    me_walk<R, 16, ME_LEAD>( rbase, (int)(rs / 4), ring, fold );
 }
 
 // ---------------------------------------------------------------------------
-// 10 bit: a lane owns two adjacent candidate columns (2g, 2g+1; the first is dword aligned
-// for even R) and half of the fenc rows (lane pair h = 0/1: rows 8h..8h+7); per ref row it
-// loads 9 dwords once (L rows ahead), forms the odd column's dwords with one
-// v_alignbyte_b32 each, and folds the row into <= 8 candidates x 2 columns with v_sad_u16.
-// `sink( c, a0, a1 )` receives candidate row c's two finished SADs (columns 2g, 2g+1),
-// identical in both lanes of the pair after the DPP add.
-template <int R, int L, int Y, class Sink>
-__device__ __forceinline__ void me_row5p( const uint32_t *__restrict__ rbase, int rs_dw, const uint32_t (&F)[8][8],
-                                          uint32_t (&acc)[8][2], Sink &sink, uint32_t (&ring)[L][9] )
-{
-    constexpr int C0 = Y - 7 > 0 ? Y - 7 : 0;
-    constexpr int C1 = Y < 2 * R ? Y : 2 * R;
-    uint32_t w[9], o[8];
-#pragma unroll
-    for( int k = 0; k < 9; k++ )
-        w[k] = ring[Y % L][k];
-    if constexpr( Y + L < 2 * R + 8 )
-    {
-        const uint32_t *row = rbase + (Y + L) * rs_dw;
-#pragma unroll
-        for( int k = 0; k < 9; k++ )
-            ring[Y % L][k] = row[k];
-    }
-#pragma unroll
-    for( int k = 0; k < 8; k++ )
-        o[k] = __builtin_amdgcn_alignbyte( w[k + 1], w[k], 2 );
-#pragma unroll
-    for( int c = C0; c <= C1; c++ )
-    {
-        const int r = Y - c;
-        uint32_t a0 = r == 0 ? 0u : acc[c & 7][0], a1 = r == 0 ? 0u : acc[c & 7][1];
-#pragma unroll
-        for( int k = 0; k < 8; k++ )
-        {
-            a0 = __builtin_amdgcn_sad_u16( F[r][k], w[k], a0 );
-            a1 = __builtin_amdgcn_sad_u16( F[r][k], o[k], a1 );
-        }
-        if( r == 7 )
-        {
-            a0 += (uint32_t)__builtin_amdgcn_update_dpp( 0, (int)a0, 0xB1, 0xF, 0xF, false );
-            a1 += (uint32_t)__builtin_amdgcn_update_dpp( 0, (int)a1, 0xB1, 0xF, 0xF, false );
-            sink( c, a0, a1 );
-        }
-        else
-        {
-            acc[c & 7][0] = a0;
-            acc[c & 7][1] = a1;
-        }
-    }
-    __builtin_amdgcn_sched_barrier( 0 );
-}
-
-template <int R, int L, class Sink, int... Ys>
-__device__ __forceinline__ void me_rows5p( const uint32_t *__restrict__ rbase, int rs_dw, const uint32_t (&F)[8][8],
-                                           uint32_t (&acc)[8][2], Sink &sink, std::integer_sequence<int, Ys...> )
-{
-    uint32_t ring[L][9];
-#pragma unroll
-    for( int j = 0; j < L; j++ )
-#pragma unroll
-        for( int k = 0; k < 9; k++ )
-            ring[j][k] = rbase[j * rs_dw + k];
-    ( me_row5p<R, L, Ys>( rbase, rs_dw, F, acc, sink, ring ), ... );
-}
-
+// 10 bit: column-pair lanes (ring_p, fold_pair).
 // G column pairs per MB (full: R+1, centred: cen_cols(10, R) / 2), row pitch P
 template <int R, int G, int P>
 __global__ __launch_bounds__( 256 ) void me_full_sad16_v5_kernel( const uint16_t *__restrict__ fenc, intptr_t fs,
@@ -551,111 +640,34 @@ __global__ __launch_bounds__( 256 ) void me_full_sad16_v5_kernel( const uint16_t
                                                                   const int16_t *__restrict__ centre,
                                                                   int16_t *__restrict__ origin, int xcd )
 {
-    // 32-bit index decomposition as in v7 (the launcher keeps the lane count below 2^32)
-    const uint32_t blk = xcd ? xcd_block( blockIdx.x, gridDim.x ) : blockIdx.x;
-    const uint32_t slot = blk * blockDim.x + threadIdx.x;
-    if( slot >= (uint32_t)nframes * (uint32_t)mbh * (uint32_t)mbw * (uint32_t)(2 * G) )
+    const me_lane l = me_lane_of<2 * G, true>( xcd, nframes, mbh, mbw );
+    if( !l.live )
         return;
-    const int h = (int)(slot & 1);
-    const uint32_t mb32 = slot / (2 * G), t32 = mb32 / (uint32_t)mbw, f32 = t32 / (uint32_t)mbh;
-    const int grp = (int)((slot >> 1) - mb32 * G);
-    const int mbx = (int)(mb32 - t32 * (uint32_t)mbw);
-    const int mby = (int)(t32 - f32 * (uint32_t)mbh);
-    const int64_t mb = mb32, f = f32;
 
     uint32_t F[8][8];
-    const uint32_t *fe = (const uint32_t *)(fenc + f * ffs + (intptr_t)(16 * mby + 8 * h) * fs + 16 * mbx);
-    const int fs_dw = (int)(fs / 2);
-#pragma unroll
-    for( int r = 0; r < 8; r++ )
-#pragma unroll
-        for( int k = 0; k < 8; k++ )
-            F[r][k] = fe[r * fs_dw + k];
+    load_fenc( F, (const uint32_t *)(fenc + l.f * ffs + (intptr_t)(16 * l.mby + 8 * l.h) * fs + 16 * l.mbx),
+               (int)(fs / 2) );
     int ox, oy;
-    me_window<10, R, P>( centre, mb, mbx, mby, mbw, mbh, ox, oy );
-    if( origin && grp == 0 && h == 0 )
+    me_window<10, R, P>( centre, l.mb, l.mbx, l.mby, mbw, mbh, ox, oy );
+    if( origin && l.grp == 0 && l.h == 0 )
     {
-        origin[2 * mb] = (int16_t)ox;
-        origin[2 * mb + 1] = (int16_t)oy;
+        origin[2 * l.mb] = (int16_t)ox;
+        origin[2 * l.mb + 1] = (int16_t)oy;
     }
-    const uint32_t *rbase =
-        (const uint32_t *)(ref + f * rfs + (intptr_t)(16 * mby + 8 * h + oy) * rs + 16 * mbx + ox + 2 * grp);
-    uint32_t *out = table + mb * ((2 * R + 1) * P) + 2 * grp;
-    uint32_t acc[8][2];
+    const uint32_t *rbase = (const uint32_t *)(ref + l.f * rfs + (intptr_t)(16 * l.mby + 8 * l.h + oy) * rs +
+                                               16 * l.mbx + ox + 2 * l.grp);
+    uint32_t *out = table + l.mb * ((2 * R + 1) * P) + 2 * l.grp;
     // both lanes of the pair hold the sums and both store them (to the same address): with
     // the store predicated on h == 0 the compiler kept every row's sums live across the
     // branch -- 220 VGPRs and 2 waves per SIMD instead of 118 and 4, the round-4 regression
     // of 0.617 -> 0.71 ms per 16 1080p pairs
     auto store = [out]( int c, uint32_t a0, uint32_t a1 ) { *(uint2 *)(out + c * P) = make_uint2( a0, a1 ); };
-    me_rows5p<R, ME_LEAD>( rbase, (int)(rs / 2), F, acc, store, std::make_integer_sequence<int, 2 * R + 8>{} );
+    ring_p<ME_LEAD> ring;
+    fold_pair fold( F, store );
+    me_walk<R, 8, ME_LEAD>( rbase, (int)(rs / 2), ring, fold );
 }
 
-// 10-bit quadrant tables: the column-pair lane of the 16x16 kernel, whose fenc row half h is
-// already a quadrant row (h = 0 top, 1 bottom); the 8 dwords of a fenc row split into the
-// left (dwords 0-3) and right (4-7) accumulators, so a lane's candidate row leaves as four
-// 8x8 SADs (two columns x left / right) at fenc row 7 without the pair's DPP add.  An 8x8
-// SAD at 10 bit is at most 64 * 1023 = 65472: the quadrant tables stay uint16.
-template <int R, int L, int Y, class Sink>
-__device__ __forceinline__ void me_row5q( const uint32_t *__restrict__ rbase, int rs_dw, const uint32_t (&F)[8][8],
-                                          uint32_t (&acc)[8][4], Sink &sink, uint32_t (&ring)[L][9] )
-{
-    constexpr int C0 = Y - 7 > 0 ? Y - 7 : 0;
-    constexpr int C1 = Y < 2 * R ? Y : 2 * R;
-    uint32_t w[9], o[8];
-#pragma unroll
-    for( int k = 0; k < 9; k++ )
-        w[k] = ring[Y % L][k];
-    if constexpr( Y + L < 2 * R + 8 )
-    {
-        const uint32_t *row = rbase + (Y + L) * rs_dw;
-#pragma unroll
-        for( int k = 0; k < 9; k++ )
-            ring[Y % L][k] = row[k];
-    }
-#pragma unroll
-    for( int k = 0; k < 8; k++ )
-        o[k] = __builtin_amdgcn_alignbyte( w[k + 1], w[k], 2 );
-#pragma unroll
-    for( int c = C0; c <= C1; c++ )
-    {
-        const int r = Y - c;
-        uint32_t a[4];
-#pragma unroll
-        for( int j = 0; j < 4; j++ )
-            a[j] = r == 0 ? 0u : acc[c & 7][j];
-#pragma unroll
-        for( int k = 0; k < 4; k++ )
-        {
-            a[0] = __builtin_amdgcn_sad_u16( F[r][k], w[k], a[0] );              // column 2g, left
-            a[1] = __builtin_amdgcn_sad_u16( F[r][k], o[k], a[1] );              // column 2g+1, left
-            a[2] = __builtin_amdgcn_sad_u16( F[r][k + 4], w[k + 4], a[2] );      // column 2g, right
-            a[3] = __builtin_amdgcn_sad_u16( F[r][k + 4], o[k + 4], a[3] );      // column 2g+1, right
-        }
-        if( r == 7 )
-            sink( c, a[0] | (a[1] << 16), a[2] | (a[3] << 16) );
-        else
-        {
-#pragma unroll
-            for( int j = 0; j < 4; j++ )
-                acc[c & 7][j] = a[j];
-        }
-    }
-    __builtin_amdgcn_sched_barrier( 0 );
-}
-
-template <int R, int L, class Sink, int... Ys>
-__device__ __forceinline__ void me_rows5q( const uint32_t *__restrict__ rbase, int rs_dw, const uint32_t (&F)[8][8],
-                                           uint32_t (&acc)[8][4], Sink &sink, std::integer_sequence<int, Ys...> )
-{
-    uint32_t ring[L][9];
-#pragma unroll
-    for( int j = 0; j < L; j++ )
-#pragma unroll
-        for( int k = 0; k < 9; k++ )
-            ring[j][k] = rbase[j * rs_dw + k];
-    ( me_row5q<R, L, Ys>( rbase, rs_dw, F, acc, sink, ring ), ... );
-}
-
+// 10-bit quadrant tables: the column-pair lane with fold_quad
 template <int R>
 __global__ __launch_bounds__( 256 ) void me_full_sad8q_v5_kernel( const uint16_t *__restrict__ fenc, intptr_t fs,
                                                                   intptr_t ffs, const uint16_t *__restrict__ ref,
@@ -663,35 +675,24 @@ __global__ __launch_bounds__( 256 ) void me_full_sad8q_v5_kernel( const uint16_t
                                                                   int nframes, uint16_t *__restrict__ table8, int xcd )
 {
     constexpr int G = R + 1, P = full_pitch( R );
-    const uint32_t blk = xcd ? xcd_block( blockIdx.x, gridDim.x ) : blockIdx.x;
-    const uint32_t slot = blk * blockDim.x + threadIdx.x;
-    if( slot >= (uint32_t)nframes * (uint32_t)mbh * (uint32_t)mbw * (uint32_t)(2 * G) )
+    const me_lane l = me_lane_of<2 * G, true>( xcd, nframes, mbh, mbw );
+    if( !l.live )
         return;
-    const int h = (int)(slot & 1);
-    const uint32_t mb32 = slot / (2 * G), t32 = mb32 / (uint32_t)mbw, f32 = t32 / (uint32_t)mbh;
-    const int grp = (int)((slot >> 1) - mb32 * G);
-    const int mbx = (int)(mb32 - t32 * (uint32_t)mbw);
-    const int mby = (int)(t32 - f32 * (uint32_t)mbh);
-    const int64_t mb = mb32, f = f32;
     uint32_t F[8][8];
-    const uint32_t *fe = (const uint32_t *)(fenc + f * ffs + (intptr_t)(16 * mby + 8 * h) * fs + 16 * mbx);
-    const int fs_dw = (int)(fs / 2);
-#pragma unroll
-    for( int r = 0; r < 8; r++ )
-#pragma unroll
-        for( int k = 0; k < 8; k++ )
-            F[r][k] = fe[r * fs_dw + k];
-    const uint32_t *rbase =
-        (const uint32_t *)(ref + f * rfs + (intptr_t)(16 * mby + 8 * h - R) * rs + 16 * mbx - R + 2 * grp);
+    load_fenc( F, (const uint32_t *)(fenc + l.f * ffs + (intptr_t)(16 * l.mby + 8 * l.h) * fs + 16 * l.mbx),
+               (int)(fs / 2) );
+    const uint32_t *rbase = (const uint32_t *)(ref + l.f * rfs + (intptr_t)(16 * l.mby + 8 * l.h - R) * rs +
+                                               16 * l.mbx - R + 2 * l.grp);
     // quadrants 2h (left) and 2h + 1 (right), columns 2g, 2g+1 as one dword each
-    uint32_t *ql = (uint32_t *)(table8 + (mb * 4 + 2 * h) * ((2 * R + 1) * P) + 2 * grp);
+    uint32_t *ql = (uint32_t *)(table8 + (l.mb * 4 + 2 * l.h) * ((2 * R + 1) * P) + 2 * l.grp);
     uint32_t *qr = ql + (2 * R + 1) * P / 2;
-    auto store = [ql, qr]( int c, uint32_t l, uint32_t r ) {
-        ql[c * (P / 2)] = l;
-        qr[c * (P / 2)] = r;
+    auto store = [ql, qr]( int c, uint32_t left, uint32_t right ) {
+        ql[c * (P / 2)] = left;
+        qr[c * (P / 2)] = right;
     };
-    uint32_t acc[8][4];
-    me_rows5q<R, ME_LEAD>( rbase, (int)(rs / 2), F, acc, store, std::make_integer_sequence<int, 2 * R + 8>{} );
+    ring_p<ME_LEAD> ring;
+    fold_quad fold( F, store );
+    me_walk<R, 8, ME_LEAD>( rbase, (int)(rs / 2), ring, fold );
 }
 
 template <int BD>
@@ -919,13 +920,7 @@ __global__ __launch_bounds__( 256 ) void me_full_esa_v7_kernel( const uint8_t *_
         twice = !spare && grp == 0 && need;
 
     uint32_t F[16][4];
-    const uint32_t *fe = (const uint32_t *)(fenc + f * ffs + (intptr_t)(16 * mby) * fs + 16 * mbx);
-    const int fs_dw = (int)(fs / 4);
-#pragma unroll
-    for( int r = 0; r < 16; r++ )
-#pragma unroll
-        for( int k = 0; k < 4; k++ )
-            F[r][k] = fe[r * fs_dw + k];
+    load_fenc( F, (const uint32_t *)(fenc + f * ffs + (intptr_t)(16 * mby) * fs + 16 * mbx), (int)(fs / 4) );
     const uint32_t *rmb = (const uint32_t *)(ref + f * rfs + (intptr_t)(16 * mby + oy) * rs + 16 * mbx + ox);
     // key = (sad + xcost + ycost) << 12 | raster, raster = (my - min_y) * width + mx - min_x
     // < 4096, built as sat( ((sad << 12) + C[k]) + S ): C[k] = xcost << 12 | column part,
@@ -964,29 +959,31 @@ __global__ __launch_bounds__( 256 ) void me_full_esa_v7_kernel( const uint8_t *_
         key = min( min( key, k2 ), k3 );
         asm volatile( "" : "+v"( key ) );        // fold each row where its sums finish
     };
-    uint64_t acc[16];
+    ring_q<ME_LEAD> ring;
     if constexpr( TAB )
     {
         // (a lane past the last MB rewrites the last MB's values)
         uint64_t *out = (uint64_t *)(tab + mb * ((2 * R + 1) * P) + 4 * grp);
         auto store = [&out]( int c, uint32_t lo, uint32_t hi ) { out[c * (P / 4)] = ((uint64_t)hi << 32) | lo; };
+        fold_row fold( F, store );
         if( live )
         {
-            me_rows7<R, ME_LEAD>( rmb + grp, (int)(rs / 4), F, acc, store, std::make_integer_sequence<int, 2 * R + 16>{} );
+            me_walk<R, 16, ME_LEAD>( rmb + grp, (int)(rs / 4), ring, fold );
             if( twice )
             {
                 out = (uint64_t *)(tab + mb * ((2 * R + 1) * P) + 4 * G);
-                me_rows7<R, ME_LEAD>( rmb + G, (int)(rs / 4), F, acc, store, std::make_integer_sequence<int, 2 * R + 16>{} );
+                me_walk<R, 16, ME_LEAD>( rmb + G, (int)(rs / 4), ring, fold );
             }
         }
     }
     else
     {
-        me_rows7<R, ME_LEAD>( rmb + grp, (int)(rs / 4), F, acc, reduce, std::make_integer_sequence<int, 2 * R + 16>{} );
+        fold_row fold( F, reduce );
+        me_walk<R, 16, ME_LEAD>( rmb + grp, (int)(rs / 4), ring, fold );
         if( twice )
         {
             columns( G );
-            me_rows7<R, ME_LEAD>( rmb + G, (int)(rs / 4), F, acc, reduce, std::make_integer_sequence<int, 2 * R + 16>{} );
+            me_walk<R, 16, ME_LEAD>( rmb + G, (int)(rs / 4), ring, fold );
         }
         if( live && key < 0xF0000000u )
             atomicMin( &s_key[lmb], key );
@@ -1070,13 +1067,7 @@ __global__ __launch_bounds__( 256 ) void me_full_esa_v5_kernel( const uint16_t *
     const int64_t f = t / mbh;
 
     uint32_t F[8][8];
-    const uint32_t *fe = (const uint32_t *)(fenc + f * ffs + (intptr_t)(16 * mby + 8 * h) * fs + 16 * mbx);
-    const int fs_dw = (int)(fs / 2);
-#pragma unroll
-    for( int r = 0; r < 8; r++ )
-#pragma unroll
-        for( int k = 0; k < 8; k++ )
-            F[r][k] = fe[r * fs_dw + k];
+    load_fenc( F, (const uint32_t *)(fenc + f * ffs + (intptr_t)(16 * mby + 8 * h) * fs + 16 * mbx), (int)(fs / 2) );
     const int16_t *p = par + 8 * mb;
     const int bmx = p[0], bmy = p[1];
     const int min_x = max( bmx - me_range, (int)p[4] ), min_y = max( bmy - me_range, (int)p[5] );
@@ -1109,8 +1100,9 @@ __global__ __launch_bounds__( 256 ) void me_full_esa_v5_kernel( const uint16_t *
         key = min( key, k | cinv | rinv );
         asm volatile( "" : "+v"( key ) );        // fold each row where its sums finish
     };
-    uint32_t acc[8][2];
-    me_rows5p<R, ME_LEAD>( rbase, (int)(rs / 2), F, acc, reduce, std::make_integer_sequence<int, 2 * R + 8>{} );
+    ring_p<ME_LEAD> ring;
+    fold_pair fold( F, reduce );
+    me_walk<R, 8, ME_LEAD>( rbase, (int)(rs / 2), ring, fold );
     key = min( key, (uint32_t)__builtin_amdgcn_update_dpp( (int)0xFFFFFFFF, (int)key, 0xB1, 0xF, 0xF, false ) );
     if( !h && key != 0xFFFFFFFFu )
         atomicMin( keys + 3 * mb, key );
@@ -2161,26 +2153,14 @@ X264HIP_INSTANTIATE( launch_me_tesa );
 // candidates outside the template with direct SADs and merges them into the template key; at
 // range 0 me_esa8_direct_kernel scores every partition that way.  So the decisions are me.c's
 // for any inputs; the template only decides how much is shared.  10 bit runs the same passes on
-// me_row5q's column-pair lanes (R + 1 pairs from the dword-aligned origin).
+// fold_quad's column-pair lanes (R + 1 pairs from the dword-aligned origin).
 __host__ __device__ constexpr int esa8_part( int h, int s ) { return s == 0 ? 4 + 2 * h : s == 1 ? 5 + 2 * h : s == 2 ? h : 2 + h; }
 // 2R template columns: an unclipped window's (2R+3) & ~3 = 2R columns exactly
 template <int R> constexpr int esa8_groups() { return R / 2; }
-// 10 bit: column-PAIR groups (me_row5q's lane, two columns from 9 dwords a row), R + 1 of them
+// 10 bit: column-PAIR groups (fold_quad's lane, two columns from 9 dwords a row), R + 1 of them
 // from the origin aligned down to a dword (2R + 2 columns)
 template <int BD, int R> constexpr int esa8_lgroups() { return BD == 8 ? esa8_groups<R>() : R + 1; }
 template <int BD, int R> constexpr int esa8_mbs() { return 256 / (2 * esa8_lgroups<BD, R>()); }
-
-// me_window's template origin with run-time R and P (the same arithmetic)
-__device__ __forceinline__ void esa8_window( int R, int P, int cx, int cy, int mbx, int mby, int mbw, int mbh, int &ox,
-                                             int &oy, int al = 0 )
-{
-    int ax = 16 * mbx - R + cx, ay = 16 * mby - R + cy;
-    ax = min( max( ax, -32 ), 16 * mbw + 12 - P );
-    ay = min( max( ay, -32 ), 16 * mbh + 16 - 2 * R );
-    ax &= ~al;
-    ox = ax - 16 * mbx;
-    oy = ay - 16 * mby;
-}
 
 __device__ __forceinline__ uint32_t esa8_mad( uint32_t v, uint32_t c, uint32_t s4096, bool hi )
 {
@@ -2190,66 +2170,6 @@ __device__ __forceinline__ uint32_t esa8_mad( uint32_t v, uint32_t c, uint32_t s
     else
         asm( "v_mad_u32_u16 %0, %1, %2, %3" : "=v"( d ) : "v"( v ), "s"( s4096 ), "v"( c ) );
     return d;
-}
-
-// rbase: the dword holding the lane's first window byte, sh: that byte's offset in it.  Each row
-// is six aligned dwords (the 20 bytes the lane's windows span, at any offset) realigned with
-// v_alignbyte: a misaligned 16-byte load costs the address path 4x an aligned one
-// (profiles/r01d_ta_probe.txt), which made the template pass address-bound off the dword grid.
-template <int R, int L, int Y, class Sink>
-__device__ __forceinline__ void me_row_e8( const uint32_t *__restrict__ rbase, int rs_dw, uint32_t sh,
-                                           const uint32_t (&F)[8][4], uint64_t (&al)[8], uint64_t (&ar)[8],
-                                           Sink &sink, u32x4a4 (&wl)[L], u32x2a4 (&wh)[L] )
-{
-    constexpr int C0 = Y - 7 > 0 ? Y - 7 : 0;
-    constexpr int C1 = Y < 2 * R ? Y : 2 * R;
-    const u32x4a4 l4 = wl[Y % L];
-    const u32x2a4 h2 = wh[Y % L];
-    const uint32_t d0 = __builtin_amdgcn_alignbyte( l4.y, l4.x, sh ), d1 = __builtin_amdgcn_alignbyte( l4.z, l4.y, sh );
-    const uint32_t d2 = __builtin_amdgcn_alignbyte( l4.w, l4.z, sh ), d3 = __builtin_amdgcn_alignbyte( h2.x, l4.w, sh );
-    const uint32_t d4 = __builtin_amdgcn_alignbyte( h2.y, h2.x, sh );
-    const uint64_t win[4] = { (uint64_t)d1 << 32 | d0, (uint64_t)d2 << 32 | d1, (uint64_t)d3 << 32 | d2,
-                              (uint64_t)d4 << 32 | d3 };
-    if constexpr( Y + L < 2 * R + 8 )
-    {
-        const uint32_t *row = rbase + (Y + L) * rs_dw;
-        wl[Y % L] = *(const u32x4a4 *)row;
-        wh[Y % L] = *(const u32x2a4 *)(row + 4);
-    }
-#pragma unroll
-    for( int c = C0; c <= C1; c++ )
-    {
-        const int r = Y - c;
-        uint64_t a = r == 0 ? 0ull : al[c & 7], b = r == 0 ? 0ull : ar[c & 7];
-        a = __builtin_amdgcn_qsad_pk_u16_u8( win[0], F[r][0], a );
-        a = __builtin_amdgcn_qsad_pk_u16_u8( win[1], F[r][1], a );
-        b = __builtin_amdgcn_qsad_pk_u16_u8( win[2], F[r][2], b );
-        b = __builtin_amdgcn_qsad_pk_u16_u8( win[3], F[r][3], b );
-        if( r == 7 )
-            sink( c, a, b );
-        else
-        {
-            al[c & 7] = a;
-            ar[c & 7] = b;
-        }
-    }
-    __builtin_amdgcn_sched_barrier( 0 );
-}
-
-template <int R, int L, class Sink, int... Ys>
-__device__ __forceinline__ void me_rows_e8( const uint32_t *__restrict__ rbase, int rs_dw, uint32_t sh,
-                                            const uint32_t (&F)[8][4], uint64_t (&al)[8], uint64_t (&ar)[8],
-                                            Sink &sink, std::integer_sequence<int, Ys...> )
-{
-    u32x4a4 wl[L];
-    u32x2a4 wh[L];
-#pragma unroll
-    for( int k = 0; k < L; k++ )
-    {
-        wl[k] = *(const u32x4a4 *)(rbase + k * rs_dw);
-        wh[k] = *(const u32x2a4 *)(rbase + k * rs_dw + 4);
-    }
-    ( me_row_e8<R, L, Ys>( rbase, rs_dw, sh, F, al, ar, sink, wl, wh ), ... );
 }
 
 typedef uint16_t u16x2 __attribute__( ( ext_vector_type( 2 ) ) );
@@ -2497,8 +2417,9 @@ __global__ __launch_bounds__( 256 ) void me_esa8_kernel( const typename PT<BD>::
     const int mbx = (int)(mb32 - t32 * (uint32_t)mbw), mby = (int)(t32 - f32 * (uint32_t)mbh);
     const int64_t mb = mb32, f = f32;
     int ox, oy;
-    esa8_window( R, P, centre ? centre[2 * mb] : 0, centre ? centre[2 * mb + 1] : 0, mbx, mby, mbw, mbh, ox, oy,
-                 BD == 8 ? 0 : 1 );
+    // (8 bit: no alignment, ring_qu realigns the rows)
+    me_window( R, P, BD == 8 ? 0 : 1, centre ? centre[2 * mb] : 0, centre ? centre[2 * mb + 1] : 0, mbx, mby, mbw, mbh,
+               ox, oy );
     // the partitions' windows (the MB's lanes, 2G of them: 6 at R = 4), the template origin,
     // the key slots
     if( !spare )
@@ -2570,17 +2491,12 @@ __global__ __launch_bounds__( 256 ) void me_esa8_kernel( const typename PT<BD>::
       if constexpr( BD == 8 )
       {
         uint32_t F[8][4];
-        const uint32_t *fe = (const uint32_t *)(fenc + f * ffs + (intptr_t)(16 * mby + 8 * h) * fs + 16 * mbx);
-        const int fs_dw = (int)(fs / 4);
-#pragma unroll
-        for( int r = 0; r < 8; r++ )
-#pragma unroll
-            for( int k = 0; k < 4; k++ )
-                F[r][k] = fe[r * fs_dw + k];
+        load_fenc( F, (const uint32_t *)(fenc + f * ffs + (intptr_t)(16 * mby + 8 * h) * fs + 16 * mbx), (int)(fs / 4) );
         // (the window's first byte: 16 mbx + ox + 4 grp; its dword and offset, 16 mbx being a multiple of 4)
         const uint32_t *rbase = (const uint32_t *)(ref + f * rfs + (intptr_t)(16 * mby + 8 * h + oy) * rs + 16 * mbx +
                                                    (ox & ~3)) + grp;
-        const uint32_t sh = (uint32_t)ox & 3;
+        ring_qu<ME_LEAD> ring;
+        ring.sh = (uint32_t)ox & 3;
         const uint32_t s4096 = 4096u;
         __attribute__( ( address_space( 3 ) ) ) uint32_t *srow =
             (__attribute__( ( address_space( 3 ) ) ) uint32_t *)(s_row + lmb * W * 8 + 4 * h);
@@ -2593,7 +2509,8 @@ __global__ __launch_bounds__( 256 ) void me_esa8_kernel( const typename PT<BD>::
             const uint32_t m = min( min( min( k0, k1 ), k2 ), k3 );
             k = min( k, __builtin_elementwise_add_sat( m, S ) );
         };
-        auto sink = [&]( int c, uint64_t a, uint64_t b ) {
+        // (the lane folds one half of the MB: fold_lr's half index is always 0)
+        auto sink = [&]( int c, int, uint64_t a, uint64_t b ) {
             __attribute__( ( address_space( 3 ) ) ) uint32_t *q = srow;
             asm volatile( "" : "+v"( q ) );     // read where the row finishes
             typedef uint32_t u32x4 __attribute__( ( ext_vector_type( 4 ) ) );
@@ -2611,22 +2528,16 @@ __global__ __launch_bounds__( 256 ) void me_esa8_kernel( const typename PT<BD>::
             fold( pk_add_u16x4( mine, recv ), C[3], S.w, key[3] );
             asm volatile( "" : "+v"( key[0] ), "+v"( key[1] ), "+v"( key[2] ), "+v"( key[3] ) );
         };
-        uint64_t al[8], ar[8];
-        me_rows_e8<R, ME_LEAD>( rbase, (int)(rs / 4), sh, F, al, ar, sink, std::make_integer_sequence<int, 2 * R + 8>{} );
+        fold_lr halves( F, sink );
+        me_walk<R, 8, ME_LEAD>( rbase, (int)(rs / 4), ring, halves );
       }
       else
       {
-        // 10 bit: me_row5q's lane (fenc row half h, columns 2 grp, 2 grp + 1 of the dword-aligned
+        // 10 bit: fold_quad's lane (fenc row half h, columns 2 grp, 2 grp + 1 of the dword-aligned
         // template), its candidate row's quadrants as two packed u16 pairs; 16x8 / 8x16 sums (up to
         // 130944) and keys in 32-bit lanes
         uint32_t F[8][8];
-        const uint32_t *fe = (const uint32_t *)(fenc + f * ffs + (intptr_t)(16 * mby + 8 * h) * fs + 16 * mbx);
-        const int fs_dw = (int)(fs / 2);
-#pragma unroll
-        for( int r = 0; r < 8; r++ )
-#pragma unroll
-            for( int k = 0; k < 8; k++ )
-                F[r][k] = fe[r * fs_dw + k];
+        load_fenc( F, (const uint32_t *)(fenc + f * ffs + (intptr_t)(16 * mby + 8 * h) * fs + 16 * mbx), (int)(fs / 2) );
         const uint32_t *rbase =
             (const uint32_t *)(ref + f * rfs + (intptr_t)(16 * mby + 8 * h + oy) * rs + 16 * mbx + ox + 2 * grp);
         __attribute__( ( address_space( 3 ) ) ) uint32_t *srow =
@@ -2650,8 +2561,9 @@ __global__ __launch_bounds__( 256 ) void me_esa8_kernel( const typename PT<BD>::
             fold2( (mine & 0xffff) + (recv & 0xffff), (mine >> 16) + (recv >> 16), C[3], S.w, key[3] );
             asm volatile( "" : "+v"( key[0] ), "+v"( key[1] ), "+v"( key[2] ), "+v"( key[3] ) );
         };
-        uint32_t acc[8][4];
-        me_rows5q<R, ME_LEAD>( rbase, (int)(rs / 2), F, acc, sink, std::make_integer_sequence<int, 2 * R + 8>{} );
+        ring_p<ME_LEAD> ring;
+        fold_quad fold( F, sink );
+        me_walk<R, 8, ME_LEAD>( rbase, (int)(rs / 2), ring, fold );
       }
         if( live )
 #pragma unroll
