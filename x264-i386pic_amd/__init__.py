@@ -30,6 +30,7 @@ __all__ = [
     "CMP_SAD", "CMP_SSD", "CMP_SATD", "CPU_HIP", "set_variant", "set_thread_device", "thread_device",
     "backend_banner", "forward_ref", "upload", "me_bind", "MeBinding", "weight_scale_plane", "stream_pair", "stream_pair_destroy", "me_search_full8",
     "me_search_ref_tesa", "me_refine_bidir", "me_refine_qpel_refdupe", "plane_upload", "upload_plane", "upload_planes",
+    "mbtree_propagate", "mbtree_finish", "mbtree_plan", "mbtree_step", "MbtreeStep",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -334,9 +335,10 @@ def cqm_dequant(scaling_lists, transform_8x8=True):
 
 
 # ----------------------------------------------------------------- declarations
-# Every function of include/x264hip.h, once: "return:parameters", one letter each, in the
-# struct module's spelling where it has one.  tests/test_abi.py checks both tables against
-# the header's prototypes.
+# Every function of include/x264hip.h and include/x264hip_mbtree.h, once: "return:parameters",
+# one letter each, in the struct module's spelling where it has one.  tests/test_abi.py checks
+# the first two tables against x264hip.h's prototypes, tests/test_cpu_mbtree.py the third against
+# x264hip_mbtree.h's.
 _KINDS = {"P": _P,             # any pointer or array parameter
           "n": _IP,            # intptr_t
           "i": _c.c_int,
@@ -344,6 +346,7 @@ _KINDS = {"P": _P,             # any pointer or array parameter
           "N": _c.c_size_t,
           "q": _c.c_int64,
           "s": _c.c_char_p,    # const char *
+          "f": _c.c_float,
           "v": None}           # void (return only)
 # x264hip_<name>
 _PLAIN = {
@@ -436,6 +439,11 @@ _PER_DEPTH = {
     "weights_analyse": "i:PPniiPPiPPnPPPPiiiiiiPPPP",
     "frame_init_lowres": "i:PnniiiPnnP",
 }
+# include/x264hip_mbtree.h: x264hip_mbtree_<name>
+_MBTREE = {
+    "propagate": "i:PiiiP",
+    "finish": "i:PPPPPiiffP",
+}
 
 
 def _declare(L):
@@ -448,6 +456,8 @@ def _declare(L):
     for name, sig in _PER_DEPTH.items():
         for bd in (8, 10):
             declare(getattr(L, f"x264hip_{bd}_{name}"), sig)
+    for name, sig in _MBTREE.items():
+        declare(getattr(L, f"x264hip_mbtree_{name}"), sig)
 
 
 # ----------------------------------------------------------------- CQM
@@ -999,6 +1009,143 @@ def lowres_status():
     timed out in the band wavefront (x264hip_lowres_status; reporting clears it)."""
     f = lib().x264hip_lowres_status
     _rc(f(_stream()), "lowres_status")
+
+
+# ----------------------------------------------------------------- MB-tree (include/x264hip_mbtree.h)
+class MbtreeStep(_c.Structure):
+    """x264hip_mbtree_step_t: one macroblock_tree_propagate(p0, p1, b, referenced) step"""
+    _fields_ = [("intra_cost", _P), ("lowres_costs", _P), ("inv_qscale", _P), ("propagate_in", _P),
+                ("mvs", _P * 2), ("ref_costs", _P * 2), ("fps_factor", _c.c_float), ("bipred_weight", _c.c_int32)]
+
+
+def mbtree_step(intra_cost, lowres_costs, mvs0, ref_costs0, fps_factor, mvs1=None, ref_costs1=None,
+                inv_qscale=None, propagate_in=None, bipred_weight=32):
+    """One step for mbtree_propagate from device tensors of frame b: intra_cost / lowres_costs
+    (lowres_costs[b-p0][p1-b]) / inv_qscale / propagate_in (b's own i_propagate_cost when it is
+    referenced, else None) uint16-as-int16 [mbs], mvs_l int16 [mbs, 2], ref_costs_l the
+    i_propagate_cost planes of p0 / p1 (read-modify-write); list 1 is left out when b == p1.
+    The step keeps its tensors alive."""
+    for t in (intra_cost, lowres_costs, mvs0, ref_costs0, mvs1, ref_costs1, inv_qscale, propagate_in):
+        if t is not None and not (t.is_cuda and t.is_contiguous() and t.element_size() == 2):
+            raise ValueError("mbtree_step: 16-bit contiguous device tensors")
+    if (mvs1 is None) != (ref_costs1 is None):
+        raise ValueError("mbtree_step: mvs1 and ref_costs1 go together")
+
+    def a(t):
+        return None if t is None else t.data_ptr()
+    st = MbtreeStep(a(intra_cost), a(lowres_costs), a(inv_qscale), a(propagate_in), (_P * 2)(a(mvs0), a(mvs1)),
+                    (_P * 2)(a(ref_costs0), a(ref_costs1)), float(fps_factor), int(bipred_weight))
+    st._keep = (intra_cost, lowres_costs, mvs0, ref_costs0, mvs1, ref_costs1, inv_qscale, propagate_in)
+    return st
+
+
+def mbtree_propagate(steps, mb_width, mb_height):
+    """x264hip_mbtree_propagate: the mbtree_step() records of one call on the current stream.  The
+    steps may share destination planes (the B frames between two non-B frames); none may read a
+    plane another writes."""
+    arr = (MbtreeStep * max(1, len(steps)))(*steps)
+    _rc(lib().x264hip_mbtree_propagate(arr, len(steps), mb_width, mb_height, _stream()), "mbtree_propagate")
+
+
+def mbtree_finish(intra_cost, propagate_cost, qp_offset_aq, fps_factor, weightdelta, strength, inv_qscale=None,
+                  qp_offset=None):
+    """x264hip_mbtree_finish: macroblock_tree_finish of one frame; float32 qp_offset [mbs]
+    (qp_offset_aq itself for the in-place form; elements whose scaled intra cost is 0 are not
+    written).  fps_factor is the integer of slicetype.c:1031."""
+    import torch
+    n = intra_cost.numel()
+    if qp_offset is None:
+        qp_offset = torch.empty_like(qp_offset_aq)
+    if qp_offset_aq.dtype != torch.float32 or qp_offset.dtype != torch.float32 or propagate_cost.numel() != n \
+            or qp_offset_aq.numel() != n or qp_offset.numel() != n:
+        raise ValueError("mbtree_finish: float32 offsets and one element per MB everywhere")
+    _rc(lib().x264hip_mbtree_finish(_ptr(intra_cost), None if inv_qscale is None else _ptr(inv_qscale),
+                                    _ptr(propagate_cost), _ptr(qp_offset_aq), _ptr(qp_offset), n, int(fps_factor),
+                                    float(weightdelta), float(strength), _stream()), "mbtree_finish")
+    return qp_offset
+
+
+def mbtree_plan(types, bframe_pyramid=False, vbv=False, b_intra=True):
+    """The ordered operations of macroblock_tree (reference encoder/slicetype.c:1091-1184, the
+    i_lookahead > 0 branch) for a lookahead window whose frames 0..len(types)-1 have the types
+    `types` (a string or sequence of 'I' / 'P' / 'B'; frame 0 is the I or P frame the window
+    starts from).  Pure host code.  Returns a list of
+
+      ("zero", f)                 memset frames[f]->i_propagate_cost
+      ("cost", p0, p1, b)         slicetype_frame_cost( p0, p1, b ) must have run
+      ("propagate", steps)        one x264hip_mbtree_propagate call; steps = [(p0, p1, b, referenced)]
+      ("finish", f, ref0_distance) macroblock_tree_finish of frame f
+
+    in an order that respects every dependency of the reference's loop.  The unreferenced B
+    frames between two non-B frames share one propagate call: they write the same planes and
+    read none of them.  A referenced step (the pyramid's middle B, the trailing non-B frame)
+    reads the plane the earlier calls wrote, so it is a call of its own.  With vbv the reference
+    finishes every referenced frame right after its step (slicetype.c:1087-1088).
+
+    `IBBP`: cost (0,0,0); zero 3; cost (0,3,3); zero 0; cost (0,3,2), (0,3,1); propagate
+    [(0,3,2,False), (0,3,1,False)]; propagate [(0,3,3,True)]; finish (0, 0)."""
+    isb = [str(t).upper() == "B" for t in types]
+    num_frames = len(isb) - 1
+    ops = []
+    idx = 0 if b_intra else 1
+    bframes = 0
+
+    def propagate(steps):
+        ops.append(("propagate", steps))
+        if vbv:
+            for p0, p1, b, referenced in steps:
+                if referenced:
+                    ops.append(("finish", b, b - p0 if b == p1 else 0))
+
+    i = num_frames
+    if b_intra:
+        ops.append(("cost", 0, 0, 0))
+    while i > 0 and isb[i]:
+        i -= 1
+    last_nonb = i
+    if last_nonb < idx:
+        return ops
+    ops.append(("zero", last_nonb))
+    while True:
+        i -= 1
+        if i + 1 <= idx:
+            break
+        cur_nonb = i
+        while isb[cur_nonb] and cur_nonb > 0:
+            cur_nonb -= 1
+        if cur_nonb < idx:
+            break
+        ops.append(("cost", cur_nonb, last_nonb, last_nonb))
+        ops.append(("zero", cur_nonb))
+        bframes = last_nonb - cur_nonb - 1
+        group = []
+        if bframe_pyramid and bframes > 1:
+            middle = (bframes + 1) // 2 + cur_nonb
+            ops.append(("cost", cur_nonb, last_nonb, middle))
+            ops.append(("zero", middle))
+            while i > cur_nonb:
+                if i != middle:
+                    p0 = middle if i > middle else cur_nonb
+                    p1 = middle if i < middle else last_nonb
+                    ops.append(("cost", p0, p1, i))
+                    group.append((p0, p1, i, False))
+                i -= 1
+            if group:
+                propagate(group)
+            propagate([(cur_nonb, last_nonb, middle, True)])
+        else:
+            while i > cur_nonb:
+                ops.append(("cost", cur_nonb, last_nonb, i))
+                group.append((cur_nonb, last_nonb, i, False))
+                i -= 1
+            if group:
+                propagate(group)
+        propagate([(cur_nonb, last_nonb, last_nonb, True)])
+        last_nonb = cur_nonb
+    ops.append(("finish", last_nonb, last_nonb))
+    if bframe_pyramid and bframes > 1 and not vbv:
+        ops.append(("finish", last_nonb + (bframes + 1) // 2, 0))
+    return ops
 
 
 def plane_stride(width, pad=PAD):

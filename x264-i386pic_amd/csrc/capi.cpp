@@ -10,6 +10,7 @@
 // process aborts with the HIP error (there is no CPU fallback).
 #include "hipcommon.h"
 #include "x264hip.h"
+#include "x264hip_mbtree.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -1495,6 +1496,78 @@ extern "C" const char *x264hip_backend_banner( void )
 #define BD 10
 #include "capi_entries.inc"
 #undef BD
+
+// ------------------------------------------------------------ MB-tree (x264hip_mbtree.h)
+static int mbtree_device()
+{
+    int n = 0;
+    if( hipGetDeviceCount( &n ) != hipSuccess || n <= 0 )
+    {
+        (void)hipGetLastError();
+        snprintf( t_err, sizeof(t_err), "x264hip: no HIP device" );
+        return X264HIP_ENODEV;
+    }
+    return X264HIP_OK;
+}
+
+// [a, a + n) and [b, b + n) share an element
+static bool planes_overlap( const uint16_t *a, const uint16_t *b, int64_t n )
+{
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b, len = (uintptr_t)n * sizeof( uint16_t );
+    return x < y + len && y < x + len;
+}
+
+extern "C" int x264hip_mbtree_propagate( const x264hip_mbtree_step_t *steps, int n, int mb_width, int mb_height,
+                                         void *stream )
+{
+    const int64_t mbc = (int64_t)mb_width * mb_height;
+    if( !steps || n < 1 || mb_width < 1 || mb_height < 1 || mbc > ( 1 << 28 ) )
+        return X264HIP_EINVAL;
+    for( int i = 0; i < n; i++ )
+    {
+        const x264hip_mbtree_step_t &s = steps[i];
+        if( !s.intra_cost || !s.lowres_costs || !s.mvs[0] || !s.ref_costs[0] || ( s.mvs[1] && !s.ref_costs[1] ) ||
+            s.bipred_weight < 0 || s.bipred_weight > 64 )
+            return X264HIP_EINVAL;
+    }
+    // destinations against every step's source plane and against each other
+    for( int i = 0; i < n; i++ )
+        for( int l = 0; l < ( steps[i].mvs[1] ? 2 : 1 ); l++ )
+        {
+            const uint16_t *d = steps[i].ref_costs[l];
+            for( int j = 0; j < n; j++ )
+            {
+                if( steps[j].propagate_in && planes_overlap( d, steps[j].propagate_in, mbc ) )
+                {
+                    snprintf( t_err, sizeof(t_err), "x264hip_mbtree_propagate: step %d writes the plane step %d reads",
+                              i, j );
+                    return X264HIP_EINVAL;
+                }
+                for( int m = 0; m < ( steps[j].mvs[1] ? 2 : 1 ); m++ )
+                    if( d != steps[j].ref_costs[m] && planes_overlap( d, steps[j].ref_costs[m], mbc ) )
+                    {
+                        snprintf( t_err, sizeof(t_err), "x264hip_mbtree_propagate: destination planes overlap" );
+                        return X264HIP_EINVAL;
+                    }
+            }
+        }
+    if( int rc = mbtree_device() )
+        return rc;
+    return map_err( launch_mbtree_propagate( steps, n, mb_width, mb_height, (hipStream_t)stream ), "mbtree_propagate" );
+}
+
+extern "C" int x264hip_mbtree_finish( const uint16_t *intra_cost, const uint16_t *inv_qscale,
+                                      const uint16_t *propagate_cost, const float *qp_offset_aq, float *qp_offset,
+                                      int mb_count, int fps_factor, float weightdelta, float strength, void *stream )
+{
+    if( !intra_cost || !propagate_cost || !qp_offset_aq || !qp_offset || mb_count < 1 || fps_factor < 1 )
+        return X264HIP_EINVAL;
+    if( int rc = mbtree_device() )
+        return rc;
+    return map_err( launch_mbtree_finish( intra_cost, inv_qscale, propagate_cost, qp_offset_aq, qp_offset, mb_count,
+                                          fps_factor, weightdelta, strength, (hipStream_t)stream ),
+                    "mbtree_finish" );
+}
 
 // dequant4_mf / dequant8_mf of x264_cqm_init, reference common/set.c:31-39,
 // 52-61, 124-159 (host-side table set-up, the input of the dequant entries)

@@ -650,3 +650,12 @@ hipError_t launch_lowres_bidir( const typename PT<BD>::pixel *fenc, intptr_t ffs
                                 const uint16_t *invq, uint16_t *lowres_costs, int32_t *row_satd, int32_t *est,
                                 int nslices, hipStream_t stream );
 } // namespace x264hip
+
+// MB-tree (mbtree.hip; include/x264hip_mbtree.h)
+struct x264hip_mbtree_step_t;
+namespace x264hip {
+hipError_t launch_mbtree_propagate( const x264hip_mbtree_step_t *steps, int n, int mbw, int mbh, hipStream_t stream );
+hipError_t launch_mbtree_finish( const uint16_t *intra, const uint16_t *invq, const uint16_t *prop, const float *aq,
+                                 float *out, int mbc, int fps_factor, float weightdelta, float strength,
+                                 hipStream_t stream );
+} // namespace x264hip
