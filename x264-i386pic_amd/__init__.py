@@ -31,6 +31,7 @@ __all__ = [
     "backend_banner", "forward_ref", "upload", "me_bind", "MeBinding", "weight_scale_plane", "stream_pair", "stream_pair_destroy", "me_search_full8",
     "me_search_ref_tesa", "me_refine_bidir", "me_refine_qpel_refdupe", "plane_upload", "upload_plane", "upload_planes",
     "mbtree_propagate", "mbtree_finish", "mbtree_plan", "mbtree_step", "MbtreeStep",
+    "mb_mc", "Mc",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -335,10 +336,11 @@ def cqm_dequant(scaling_lists, transform_8x8=True):
 
 
 # ----------------------------------------------------------------- declarations
-# Every function of include/x264hip.h and include/x264hip_mbtree.h, once: "return:parameters",
-# one letter each, in the struct module's spelling where it has one.  tests/test_abi.py checks
-# the first two tables against x264hip.h's prototypes, tests/test_cpu_mbtree.py the third against
-# x264hip_mbtree.h's.
+# Every function of include/x264hip.h, include/x264hip_mbtree.h and include/x264hip_mc.h, once:
+# "return:parameters", one letter each, in the struct module's spelling where it has one.
+# tests/test_abi.py checks the first two tables against x264hip.h's prototypes,
+# tests/test_cpu_mbtree.py the third against x264hip_mbtree.h's, tests/test_cpu_mc.py the fourth
+# against x264hip_mc.h's.
 _KINDS = {"P": _P,             # any pointer or array parameter
           "n": _IP,            # intptr_t
           "i": _c.c_int,
@@ -444,6 +446,10 @@ _MBTREE = {
     "propagate": "i:PiiiP",
     "finish": "i:PPPPPiiffP",
 }
+# include/x264hip_mc.h: x264hip_8_<name> and x264hip_10_<name>
+_MC = {
+    "mb_mc": "i:PiPPPiP",
+}
 
 
 def _declare(L):
@@ -458,6 +464,9 @@ def _declare(L):
             declare(getattr(L, f"x264hip_{bd}_{name}"), sig)
     for name, sig in _MBTREE.items():
         declare(getattr(L, f"x264hip_mbtree_{name}"), sig)
+    for name, sig in _MC.items():
+        for bd in (8, 10):
+            declare(getattr(L, f"x264hip_{bd}_{name}"), sig)
 
 
 # ----------------------------------------------------------------- CQM
@@ -1146,6 +1155,74 @@ def mbtree_plan(types, bframe_pyramid=False, vbv=False, b_intra=True):
     if bframe_pyramid and bframes > 1 and not vbv:
         ops.append(("finish", last_nonb + (bframes + 1) // 2, 0))
     return ops
+
+
+# ----------------------------------------------------------------- motion compensation (include/x264hip_mc.h)
+class McRef(_c.Structure):
+    """x264hip_mc_ref_t: one reference picture's planes at pixel (0,0) of frame 0"""
+    _fields_ = [("luma", _P * 4), ("chroma", _P * 8)]
+
+
+class Mc(_c.Structure):
+    """x264hip_mc_t"""
+    _fields_ = [("chroma_format", _c.c_int32), ("ref", McRef * 2), ("ref_stride", _IP), ("ref_frame_stride", _IP),
+                ("ref_chroma_stride", _IP), ("ref_chroma_frame_stride", _IP), ("weight", Weight * 3),
+                ("pred", _P), ("pred_stride", _IP), ("pred_frame_stride", _IP), ("pred_chroma", _P * 2),
+                ("pred_chroma_stride", _IP), ("pred_chroma_frame_stride", _IP)]
+
+
+def mb_mc(planes0, planes1, ref_origin, ref_stride, i_pixel, pos, par, mode=None, chroma=None,
+          weight=(None, None, None), outs=None):
+    """x264_mb_mc (common/macroblock.c:31-246) of n equally sized partitions (x264hip_*_mb_mc):
+    planes0 / planes1 = [F, H, V, C] of the list 0 / list 1 references ([n, rows, stride] each, pixel
+    (0,0) at ref_origin; planes1 None when no block uses list 1), pos int32 [n, 3] = (frame, x, y)
+    as the searches take it, par int16 [n, 8] = (mv0 x, y, mv1 x, y, mv_min x, y, mv_max x, y), mode
+    int32 [n] = lists | (bipred_weight << 8) or None (list 0 everywhere).
+    chroma = (chroma_format, ref_chroma0, ref_chroma1, chroma_origin, chroma_stride) with
+    ref_chroma_l = [NV12 / NV16 tensor] (4:2:0 / 4:2:2) or U's F, H, V, C then V's (4:4:4), None for
+    an unused list 1; chroma None = luma only.  weight[p] = (scale, denom, offset) or None
+    (h->sh.weight[i_ref][p], list-0-only blocks).
+    outs = (pred, pred_origin, pred_stride, pred_chroma, pred_chroma_origin, pred_chroma_stride)
+    with pred_chroma = [UV tensor] or [U, V]; None allocates zeroed planes shaped like the
+    references.  Returns (pred, pred_chroma list)."""
+    import torch
+    bd = _pix_bd(planes0[0])
+    cf, rc0, rc1, c_origin, c_stride = chroma if chroma is not None else (0, (), (), 0, 0)
+    rc0, rc1 = list(rc0 or ()), list(rc1 or ())
+    if outs is None:
+        pred = torch.zeros_like(planes0[0])
+        pred_c = [torch.zeros_like(rc0[0]) for _ in range(2 if cf == 3 else 1 if cf else 0)]
+        p_origin, p_stride, pc_origin, pc_stride = ref_origin, ref_stride, c_origin, c_stride
+    else:
+        pred, p_origin, p_stride, pred_c, pc_origin, pc_stride = outs
+        pred_c = list(pred_c or ())
+    m = Mc()
+    m.chroma_format = int(cf)
+    for l, (luma, chr_) in enumerate(((planes0, rc0), (planes1 or (), rc1))):
+        for k, t in enumerate(luma):
+            m.ref[l].luma[k] = _ptr(t, ref_origin).value
+        for k, t in enumerate(chr_):
+            m.ref[l].chroma[k] = _ptr(t, c_origin).value
+    m.ref_stride = ref_stride
+    m.ref_frame_stride = _frame_stride(*planes0, *(planes1 or ()))
+    if rc0 or rc1:
+        m.ref_chroma_stride = c_stride
+        m.ref_chroma_frame_stride = _frame_stride(*rc0, *rc1)
+    for k, w in enumerate(weight):
+        if w is not None:
+            m.weight[k] = Weight(1, *[int(v) for v in w])
+    m.pred, m.pred_stride, m.pred_frame_stride = _ptr(pred, p_origin).value, p_stride, _frame_stride(pred)
+    for k, t in enumerate(pred_c):
+        m.pred_chroma[k] = _ptr(t, pc_origin).value
+    if pred_c:
+        m.pred_chroma_stride, m.pred_chroma_frame_stride = pc_stride, _frame_stride(*pred_c)
+    n = pos.shape[0]
+    name = f"x264hip_{bd}_mb_mc"
+    # (torch gives an empty tensor a NULL pointer; with n == 0 the arrays are not read)
+    arrays = [_ptr(t) if n else _c.c_void_p(_c.addressof(m)) for t in (pos, par)]
+    _rc(getattr(lib(), name)(_c.byref(m), i_pixel, *arrays, _ptr(mode) if mode is not None and n else None,
+                             n, _stream()), name)
+    return pred, pred_c
 
 
 def plane_stride(width, pad=PAD):

@@ -11,6 +11,7 @@
 #include "hipcommon.h"
 #include "x264hip.h"
 #include "x264hip_mbtree.h"
+#include "x264hip_mc.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -1498,7 +1499,7 @@ extern "C" const char *x264hip_backend_banner( void )
 #undef BD
 
 // ------------------------------------------------------------ MB-tree (x264hip_mbtree.h)
-static int mbtree_device()
+static int any_device()
 {
     int n = 0;
     if( hipGetDeviceCount( &n ) != hipSuccess || n <= 0 )
@@ -1551,7 +1552,7 @@ extern "C" int x264hip_mbtree_propagate( const x264hip_mbtree_step_t *steps, int
                     }
             }
         }
-    if( int rc = mbtree_device() )
+    if( int rc = any_device() )
         return rc;
     return map_err( launch_mbtree_propagate( steps, n, mb_width, mb_height, (hipStream_t)stream ), "mbtree_propagate" );
 }
@@ -1562,11 +1563,69 @@ extern "C" int x264hip_mbtree_finish( const uint16_t *intra_cost, const uint16_t
 {
     if( !intra_cost || !propagate_cost || !qp_offset_aq || !qp_offset || mb_count < 1 || fps_factor < 1 )
         return X264HIP_EINVAL;
-    if( int rc = mbtree_device() )
+    if( int rc = any_device() )
         return rc;
     return map_err( launch_mbtree_finish( intra_cost, inv_qscale, propagate_cost, qp_offset_aq, qp_offset, mb_count,
                                           fps_factor, weightdelta, strength, (hipStream_t)stream ),
                     "mbtree_finish" );
+}
+
+// ------------------------------------------------------------ motion compensation (x264hip_mc.h)
+// every argument error is X264HIP_EINVAL before any HIP call; no pointer but mc is dereferenced
+template <int BD>
+static int mb_mc_entry( const x264hip_mc_t *mc, int i_pixel, const int32_t *pos, const int16_t *par,
+                        const int32_t *mode, int n, void *stream )
+{
+    if( n < 0 || !mc || !pos || !par || i_pixel < 0 || i_pixel > 6 )
+        return X264HIP_EINVAL;
+    const int cf = mc->chroma_format;
+    if( cf < 0 || cf > 3 || !mc->pred || ( cf && !mc->pred_chroma[0] ) || ( cf == 3 && !mc->pred_chroma[1] ) )
+        return X264HIP_EINVAL;
+    if( !mode )                             // list 0 everywhere: its planes must be there
+    {
+        for( int k = 0; k < 4; k++ )
+            if( !mc->ref[0].luma[k] )
+                return X264HIP_EINVAL;
+        for( int k = 0; k < ( cf == 3 ? 8 : cf ? 1 : 0 ); k++ )
+            if( !mc->ref[0].chroma[k] )
+                return X264HIP_EINVAL;
+    }
+    for( int k = 0; k < 3; k++ )
+        if( mc->weight[k].weighted && ( mc->weight[k].denom < 0 || mc->weight[k].denom > 7 ) )
+            return X264HIP_EINVAL;
+    // blocks are stored as whole dwords: outputs on 4-pixel boundaries; an interleaved reference
+    // plane on (U, V) pairs
+    const uintptr_t px = sizeof( typename PT<BD>::pixel );
+    bool bad = (uintptr_t)mc->pred % (4 * px) || mc->pred_stride % 4 || mc->pred_frame_stride % 4;
+    if( cf )
+        bad |= (uintptr_t)mc->pred_chroma[0] % (4 * px) || mc->pred_chroma_stride % 4 || mc->pred_chroma_frame_stride % 4 ||
+               ( cf == 3 && (uintptr_t)mc->pred_chroma[1] % (4 * px) );
+    if( cf == 1 || cf == 2 )
+        for( int l = 0; l < 2; l++ )
+            bad |= (uintptr_t)mc->ref[l].chroma[0] % (2 * px) || mc->ref_chroma_stride % 2 ||
+                   mc->ref_chroma_frame_stride % 2;
+    if( bad )
+    {
+        snprintf( t_err, sizeof(t_err), "x264hip_mb_mc: misaligned prediction or interleaved chroma plane" );
+        return X264HIP_EINVAL;
+    }
+    if( n == 0 )
+        return X264HIP_OK;
+    if( int rc = any_device() )
+        return rc;
+    return map_err( launch_mb_mc<BD>( mc, i_pixel, pos, par, mode, n, (hipStream_t)stream ), "mb_mc" );
+}
+
+extern "C" int x264hip_8_mb_mc( const x264hip_mc_t *mc, int i_pixel, const int32_t *pos, const int16_t *par,
+                                const int32_t *mode, int n, void *stream )
+{
+    return mb_mc_entry<8>( mc, i_pixel, pos, par, mode, n, stream );
+}
+
+extern "C" int x264hip_10_mb_mc( const x264hip_mc_t *mc, int i_pixel, const int32_t *pos, const int16_t *par,
+                                 const int32_t *mode, int n, void *stream )
+{
+    return mb_mc_entry<10>( mc, i_pixel, pos, par, mode, n, stream );
 }
 
 // dequant4_mf / dequant8_mf of x264_cqm_init, reference common/set.c:31-39,

@@ -302,6 +302,43 @@ template <int BD> __device__ __forceinline__ int upix( uint32_t w, int k )
     return BD == 8 ? (int)((w >> (8 * k)) & 0xff) : (int)((w >> (16 * k)) & 0xffff);
 }
 
+// ---- motion compensation pieces shared by the subpel refine (refine.hip) and x264_mb_mc (mbmc.hip) ----
+// get_ref's plane pair per qpel phase (mc.c:203-209, common/tables.c:183-184)
+constexpr uint8_t c_ref0[16] = { 0, 1, 1, 1, 0, 1, 1, 1, 2, 3, 3, 3, 0, 1, 1, 1 };   // x264_hpel_ref0
+constexpr uint8_t c_ref1[16] = { 0, 0, 1, 0, 2, 2, 3, 2, 2, 2, 3, 2, 2, 2, 3, 2 };   // x264_hpel_ref1
+
+// explicit weight of one plane (x264_weight_t, mc.c:117-137): rnd = 1 << (denom - 1) or 0,
+// offset already scaled by 1 << (BIT_DEPTH - 8)
+struct RsWeight
+{
+    int on, scale, denom, rnd, offset;
+};
+
+// mc_weight of packed pixels: clip( ((v * scale + rnd) >> denom) + offset ) per pixel
+template <int BD> __device__ __forceinline__ uint32_t weigh_packed( uint32_t w, const RsWeight &wt )
+{
+    constexpr int PPD = PT<BD>::PPD, SH = 32 / PPD;
+    uint32_t r = 0;
+#pragma unroll
+    for( int k = 0; k < PPD; k++ )
+    {
+        const int v = upix<BD>( w, k );
+        r |= (uint32_t)clip_pix<BD>( ((v * wt.scale + wt.rnd) >> wt.denom) + wt.offset ) << (SH * k);
+    }
+    return r;
+}
+
+// the (U, V) samples of pixel x of a row of interleaved (NV12 / NV16) words, as u16 lanes
+typedef unsigned short rs_us2 __attribute__( ( ext_vector_type( 2 ) ) );
+__device__ __forceinline__ rs_us2 as_us2( uint32_t v ) { return __builtin_bit_cast( rs_us2, v ); }
+template <int BD> __device__ __forceinline__ rs_us2 nv_pair( const uint32_t *w, int x )
+{
+    if constexpr( BD == 8 )
+        return as_us2( __builtin_amdgcn_perm( 0u, w[x >> 1], (x & 1) ? 0x0c030c02u : 0x0c010c00u ) );
+    else
+        return as_us2( w[x] );
+}
+
 } // namespace x264hip
 
 // ---- run-time switches ----
@@ -658,4 +695,12 @@ hipError_t launch_mbtree_propagate( const x264hip_mbtree_step_t *steps, int n, i
 hipError_t launch_mbtree_finish( const uint16_t *intra, const uint16_t *invq, const uint16_t *prop, const float *aq,
                                  float *out, int mbc, int fps_factor, float weightdelta, float strength,
                                  hipStream_t stream );
+} // namespace x264hip
+
+// x264_mb_mc (mbmc.hip; include/x264hip_mc.h)
+struct x264hip_mc_t;
+namespace x264hip {
+template <int BD>
+hipError_t launch_mb_mc( const x264hip_mc_t *mc, int i_pixel, const int32_t *pos, const int16_t *par,
+                         const int32_t *mode, int n, hipStream_t stream );
 } // namespace x264hip

@@ -36,35 +36,11 @@
 
 namespace x264hip {
 
-constexpr uint8_t c_ref0[16] = { 0, 1, 1, 1, 0, 1, 1, 1, 2, 3, 3, 3, 0, 1, 1, 1 };   // x264_hpel_ref0
-constexpr uint8_t c_ref1[16] = { 0, 0, 1, 0, 2, 2, 3, 2, 2, 2, 3, 2, 2, 2, 3, 2 };   // x264_hpel_ref1
-
 // subpel_iterations (me.c:38-50): { refine_hpel, refine_qpel, me_hpel, me_qpel }
 static const uint8_t k_subpel_iterations[12][4] = { { 0, 0, 0, 0 }, { 1, 1, 0, 0 }, { 0, 1, 1, 0 }, { 0, 2, 1, 0 },
                                                     { 0, 2, 1, 1 }, { 0, 2, 1, 2 }, { 0, 0, 2, 2 }, { 0, 0, 2, 2 },
                                                     { 0, 0, 4, 10 }, { 0, 0, 4, 10 }, { 0, 0, 4, 10 },
                                                     { 0, 0, 4, 10 } };
-
-// explicit weight of one plane (x264_weight_t, mc.c:117-137): rnd = 1 << (denom - 1) or 0,
-// offset already scaled by 1 << (BIT_DEPTH - 8)
-struct RsWeight
-{
-    int on, scale, denom, rnd, offset;
-};
-
-// mc_weight of packed pixels: clip( ((v * scale + rnd) >> denom) + offset ) per pixel
-template <int BD> __device__ __forceinline__ uint32_t weigh_packed( uint32_t w, const RsWeight &wt )
-{
-    constexpr int PPD = PT<BD>::PPD, SH = 32 / PPD;
-    uint32_t r = 0;
-#pragma unroll
-    for( int k = 0; k < PPD; k++ )
-    {
-        const int v = upix<BD>( w, k );
-        r |= (uint32_t)clip_pix<BD>( ((v * wt.scale + wt.rnd) >> wt.denom) + wt.offset ) << (SH * k);
-    }
-    return r;
-}
 
 // the lane's 8x4 tile of get_ref( mvx, mvy ) (weighted when WGT and wt.on) scored against its
 // fenc tile: SAD, or the sum of |coef| of the tile's two 4x4 Hadamards (even; halved by the
@@ -219,19 +195,8 @@ __device__ __forceinline__ uint32_t block4_cost( const int (&d)[4][4], bool satd
 // 2, 3, with no lane-dependent select.  s = the interleaved plane at the position's top-left U
 // sample, row 2hh; fb = the lane's two fenc rows as (U, V) pairs.  Returns U's partial cost | V's
 // << 16.
-typedef unsigned short rs_us2 __attribute__( ( ext_vector_type( 2 ) ) );
-__device__ __forceinline__ rs_us2 as_us2( uint32_t v ) { return __builtin_bit_cast( rs_us2, v ); }
 __device__ __forceinline__ x264hip_short2 as_s2( rs_us2 v ) { return __builtin_bit_cast( x264hip_short2, v ); }
 __device__ __forceinline__ uint32_t as_u32( x264hip_short2 v ) { return __builtin_bit_cast( uint32_t, v ); }
-
-template <int BD> __device__ __forceinline__ rs_us2 nv_pair( const uint32_t *w, int x )
-{
-    // the (U, V) samples of pixel x of a row of interleaved words, as u16 lanes
-    if constexpr( BD == 8 )
-        return as_us2( __builtin_amdgcn_perm( 0u, w[x >> 1], (x & 1) ? 0x0c030c02u : 0x0c010c00u ) );
-    else
-        return as_us2( w[x] );
-}
 
 template <int BD>
 __device__ __forceinline__ uint32_t nv_pair_cost( const typename PT<BD>::pixel *s, intptr_t rcs, int mvx, int mvyc,
