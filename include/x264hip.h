@@ -527,7 +527,8 @@ int x264hip_##BD##_var2_batch( int i_pixel, const pixel *fenc, intptr_t fenc_str
  * slots aliased as :1605-1608): call i reads enc_dc[4i..4i+3], sums +                          \
  * sums_off[i] (with the common `delta`), cost_mvx + cost_off[i], width[i] and                  \
  * thresh[i]; writes the passing candidate indices in order to                                  \
- * mvs[i*mvs_pitch ..] and their count to nmv[i].  Device arrays. */                            \
+ * mvs[i*mvs_pitch ..] and their count to nmv[i]; the rest of row i is not written.             \
+ * Device arrays. */                                                                            \
 int x264hip_##BD##_ads_batch( int i_pixel, const int32_t *enc_dc, const uint16_t *sums,         \
                               int delta, const int64_t *sums_off, const uint16_t *cost_mvx,     \
                               const int64_t *cost_off, const int32_t *width,                    \
@@ -628,7 +629,8 @@ int x264hip_##BD##_lowres_inter_cost_ex( const pixel *fenc, intptr_t fenc_frame_
  * over the width x height region at the pointers (the reference weights 16-wide strips while   \
  * x < width-8 and one 8-wide strip after, so up to 7 columns past width are written too);      \
  * for the lookahead, src = the lowres F plane's top-left border pixel (-32, -32), width =       \
- * lowres width + 64, height = lowres height + 64.  dst != src. */                               \
+ * lowres width + 64, height = lowres height + 64.  dst != src.  The same columns of src are     \
+ * read, and nothing else of either plane is touched. */                                        \
 int x264hip_##BD##_weight_scale_plane( pixel *dst, intptr_t dst_stride, intptr_t dst_frame_stride, \
                                        const pixel *src, intptr_t src_stride,                    \
                                        intptr_t src_frame_stride, int width, int height,         \
@@ -682,7 +684,9 @@ int x264hip_##BD##_lowres_bidir_cost_ex( const pixel *fenc, intptr_t fenc_frame_
  * [-32, lines+32) with common stride; row starts at x = -padh (PADH_ALIGN,                     \
  * frame.h:34).  Writes the 8x8 box sums of rows [1-32, lines+32-8) and columns                 \
  * [-padh, stride-padh-8) -- the values the reference leaves there -- and, when                 \
- * sub8x8, the 4x4 box sums in the second plane at +stride*(lines+64). */                        \
+ * sub8x8, the 4x4 box sums in the second plane at +stride*(lines+64), over the same rows and    \
+ * columns.  Row -32, the last 8 rows and the last 8 columns of each plane, which the           \
+ * reference uses as working storage, are not written. */                                       \
 int x264hip_##BD##_frame_integral( const pixel *plane, intptr_t stride, intptr_t frame_stride,  \
                                    int lines, int padh, int sub8x8, int n_frames,               \
                                    uint16_t *integral, intptr_t integral_frame_stride,          \
@@ -695,9 +699,12 @@ int x264hip_##BD##_frame_integral( const pixel *plane, intptr_t stride, intptr_t
  *     = sad_16x16( fenc_f + 16*(mby*fenc_stride + mbx), fenc_stride,                           \
  *                  ref_f + (16*mby + j - range)*ref_stride + 16*mbx + i - range, ref_stride )   \
  * for 0 <= i,j <= 2*range, i.e. mx = i - range, my = j - range, raster order                   \
- * my-major, row pitch P = (2*range+1 + 3) & ~3 (entries i > 2*range are padding:              \
- * the 8-bit kernel stores zeros there at range 8 and 16, and the SADs of                       \
- * mx = range+1.. at range 4 and 24).  ref must be a                                            \
+ * my-major, row pitch P = (2*range+1 + 3) & ~3 (entries i > 2*range are padding,              \
+ * and every one is written: the 8-bit kernel stores zeros there at range 8 and 16, and         \
+ * the SADs of mx = range+1.. at range 4 and 24; the 10-bit kernel stores the SAD of            \
+ * mx = range+1 and two zeros; for planes that are not dword aligned both store zeros).         \
+ * The call writes exactly the n_frames*mb_height*mb_width*(2*range+1)*P entries.               \
+ * ref must be a                                                                                \
  * padded plane (x264 PADH/PADV = 32, reference common/frame.h:32-35); every                    \
  * window row is read from x-range to x+15+range+8, so the caller keeps                        \
  * range+8 <= the horizontal padding (PADH = 32).  range is one of 4, 8, 16, 24. */             \
@@ -714,8 +721,10 @@ int x264hip_##BD##_me_search_full( const pixel *fenc, intptr_t fenc_stride,     
  * at mv (i - range, j - range), row pitch (2*range+1+3)&~3, MBs frame-major.  The 16x16         \
  * SAD is the sum of the four, PIXEL_16x8's two halves are q0+q1 / q2+q3 and PIXEL_8x16's        \
  * q0+q2 / q1+q3: the exhaustive windows of every partition me.c's ESA / TESA searches           \
- * (me.c:618-771; analyse.c:1425,1480,1546) from the absdiffs of one 16x16 search.  range       \
- * 4, 8, 16 or 24. */                                                                            \
+ * (me.c:618-771; analyse.c:1425,1480,1546) from the absdiffs of one 16x16 search.  The         \
+ * padding entries of every row are written: the 8-bit kernel stores the quadrant SADs of        \
+ * mx = range+1.. there at every range, the 10-bit kernel the SAD of mx = range+1 and two        \
+ * zeros.  range 4, 8, 16 or 24. */                                                              \
 int x264hip_##BD##_me_search_full8( const pixel *fenc, intptr_t fenc_stride,                    \
                                     intptr_t fenc_frame_stride,                                 \
                                     const pixel *ref, intptr_t ref_stride,                      \
@@ -1071,7 +1080,8 @@ int x264hip_##BD##_sub_dct_batch( int kind, const pixel *fenc, intptr_t fenc_str
                                   const int64_t *fenc_off, const int64_t *fdec_off,             \
                                   int n, dctcoef *dct, void *stream );                          \
 /* in-place DC transforms: DC_4x4 on n arrays d[16]; DC_2x4 on n pairs                          \
- * (dct[8] out, dct4x4[8][16] in/out) */                                                        \
+ * (dct[8] out, dct4x4[8][16] in/out: of it the eight DC coefficients [k][0] are written, as    \
+ * dct2x4dc zeroes them) */                                                                     \
 int x264hip_##BD##_dc_batch( int kind, dctcoef *dct, dctcoef *dct4x4, int n, void *stream );    \
 /* in-place quantisation of n blocks with one mf/bias set (device arrays of                     \
  * 16 or 64 udctcoef for 4x4/4x4x4/8x8; for the DC kinds mf[0]/bias[0] are the                  \
@@ -1106,8 +1116,9 @@ int x264hip_##BD##_add_idct_batch( int kind, pixel *dst, intptr_t dst_stride,   
  * one list's int [6][16] or [6][64] (x264hip_cqm_dequant), qp[i] per block. */                 \
 int x264hip_##BD##_dequant_batch( int kind, dctcoef *dct, const int32_t *dequant_mf,            \
                                   const int32_t *qp, int n, void *stream );                     \
-/* idct_dequant_2x4_dc (dconly = 0: writes dct4x4[8][16] per call, 128 coefs apart)             \
- * or _dconly (dconly = 1: in place on dct[8]) for n calls, qp[i] per call. */                   \
+/* idct_dequant_2x4_dc (dconly = 0: writes the eight DC coefficients dct4x4[k][0] per call,     \
+ * calls 128 coefs apart, and leaves dct[8] as it was) or _dconly (dconly = 1: in place on       \
+ * dct[8]) for n calls, qp[i] per call. */                                                       \
 int x264hip_##BD##_idct_dequant_2x4_batch( int dconly, dctcoef *dct, dctcoef *dct4x4,           \
                                            const int32_t *dequant_mf, const int32_t *qp,        \
                                            int n, void *stream );                               \
@@ -1123,7 +1134,8 @@ int x264hip_##BD##_denoise_dct_batch( dctcoef *dct, int size, int n, uint32_t *s
 int x264hip_##BD##_coef_stat_batch( int kind, const dctcoef *dct, int64_t pitch, int n,         \
                                     int32_t *out, void *stream );                               \
 /* coeff_level_run4/8/15/16 (num) of n blocks `pitch` coefs apart: last[i], mask[i],             \
- * count[i] (the return value) and level[18*i ..]. */                                           \
+ * count[i] (the return value) and the count[i] levels level[18*i ..]; the rest of the 18 is     \
+ * not written. */                                                                              \
 int x264hip_##BD##_coeff_level_run_batch( int num, const dctcoef *dct, int64_t pitch, int n,    \
                                           int32_t *last, int32_t *mask, int32_t *count,         \
                                           dctcoef *level, void *stream );                       \
@@ -1136,7 +1148,8 @@ int x264hip_##BD##_zigzag_sub_batch( int kind, int field, dctcoef *level, dctcoe
                                      const pixel *src, intptr_t src_stride, pixel *dst,         \
                                      intptr_t dst_stride, const int64_t *src_off,               \
                                      const int64_t *dst_off, int n, int32_t *nz, void *stream );\
-/* zigzag_interleave_8x8_cavlc of n blocks (64 coefs in/out, 16 nnz bytes per call). */         \
+/* zigzag_interleave_8x8_cavlc of n blocks (64 coefs in/out, 16 nnz bytes per call, of which    \
+ * the reference's four -- nnz[0], [1], [8], [9] -- are written). */                             \
 int x264hip_##BD##_zigzag_interleave_batch( dctcoef *dst, const dctcoef *src, uint8_t *nnz,     \
                                             int n, void *stream );                              \
 /* fused reconstruction of the inter luma residual (macroblock.c dequant + add16x16_idct /     \
@@ -1212,7 +1225,8 @@ int x264hip_##BD##_weight_cost_batch( int kind, const pixel *fenc, const pixel *
  * X264_WEIGHTP_FAKE).  Writes weights[3] (fenc->weight[0][0..2]), *cost_delta                   \
  * (fenc->f_weighted_cost_delta[i_delta_index], FAKE only, may be NULL) and, in the lookahead    \
  * with a luma weight, weighted_lowres (fenc->weighted[0]: at (0,0), lowres_stride, 32-pixel     \
- * border; NULL = skip) by x264_weight_scale_plane over columns [-32, width + 32) and the rows    \
+ * border; NULL = skip) by x264_weight_scale_plane over columns [-32, width + 32) (and its        \
+ * strip rounding: up to 7 more) and the rows                                                   \
  * of the 32-row border: the reference starts at buffer_lowres (-PADH_ALIGN, i.e. -64 at 8 bit,   \
  * slicetype.c:489-497), so columns [-PADH_ALIGN, -32), which no lowres search reads, keep       \
  * whatever the caller's buffer held.  Synchronous: every candidate of a plane                   \

@@ -571,23 +571,29 @@ def var2_batch(i_pixel, fenc, fenc_stride, fenc_vdelta, fdec, fdec_stride, fdec_
     return out
 
 
-def ads_batch(bitdepth, i_pixel, enc_dc, sums, delta, sums_off, cost_mvx, cost_off, width, thresh, mvs_pitch=None):
-    """n calls of ads[i_pixel]; returns (mvs int16 [n, pitch], nmv int32 [n])."""
+def ads_batch(bitdepth, i_pixel, enc_dc, sums, delta, sums_off, cost_mvx, cost_off, width, thresh, mvs_pitch=None,
+              outs=None):
+    """n calls of ads[i_pixel]; returns (mvs int16 [n, pitch], nmv int32 [n]) (outs = the two, or
+    allocated: mvs then starts as -1)."""
     import torch
     _check_bd(bitdepth)
     n = sums_off.numel()
     pitch = mvs_pitch if mvs_pitch is not None else max(1, int(width.max().item()) if n else 1)
-    mvs = torch.full((n, pitch), -1, dtype=torch.int16, device=sums.device)
-    nmv = torch.empty(n, dtype=torch.int32, device=sums.device)
+    if outs is not None:
+        mvs, nmv = outs
+    else:
+        mvs = torch.full((n, pitch), -1, dtype=torch.int16, device=sums.device)
+        nmv = torch.empty(n, dtype=torch.int32, device=sums.device)
     _rc(getattr(lib(), f"x264hip_{bitdepth}_ads_batch")(
         i_pixel, _ptr(enc_dc), _ptr(sums), delta, _ptr(sums_off), _ptr(cost_mvx), _ptr(cost_off), _ptr(width),
         _ptr(thresh), n, _ptr(mvs), pitch, _ptr(nmv), _stream()), "ads_batch")
     return mvs, nmv
 
 
-def frame_integral(planes, origin, stride, lines, padh=PAD, sub8x8=False, out=None):
+def frame_integral(planes, origin, stride, lines, padh=PAD, sub8x8=False, out=None, out_origin=None):
     """ESA integral image per frame: uint16 (as int16) [n, (2 if sub8x8 else 1) * (lines + 2*PAD), stride];
-    element [f, PAD + y, padh + x] is (x, y).  planes: [n, rows, stride] padded planes."""
+    element [f, PAD + y, padh + x] is (x, y) (or, with out_origin, `out`'s element out_origin of each frame is
+    (0, 0)).  planes: [n, rows, stride] padded planes."""
     import torch
     bd = _pix_bd(planes)
     n = planes.shape[0]
@@ -596,7 +602,8 @@ def frame_integral(planes, origin, stride, lines, padh=PAD, sub8x8=False, out=No
         out = torch.zeros((n, rows, stride), dtype=torch.int16, device=planes.device)
     _rc(getattr(lib(), f"x264hip_{bd}_frame_integral")(
         _ptr(planes, origin), stride, planes[0].numel(), lines, padh, int(bool(sub8x8)), n,
-        _ptr(out, PAD * stride + padh), out[0].numel(), _stream()), "frame_integral")
+        _ptr(out, PAD * stride + padh if out_origin is None else out_origin), out[0].numel(), _stream()),
+        "frame_integral")
     return out
 
 
@@ -624,76 +631,91 @@ def idct_dequant_2x4_batch(dconly, dct, dequant_mf, qp, dct4x4=None):
     return dct4x4 if dct4x4 is not None else dct
 
 
-def optimize_chroma_dc_batch(c422, dct, dequant_mf):
+def optimize_chroma_dc_batch(c422, dct, dequant_mf, nz=None):
     import torch
     bd = _coef_bd(dct)
     n = dequant_mf.numel()
-    nz = torch.empty(n, dtype=torch.int32, device=dct.device)
+    if nz is None:
+        nz = torch.empty(n, dtype=torch.int32, device=dct.device)
     _rc(getattr(lib(), f"x264hip_{bd}_optimize_chroma_dc_batch")(int(c422), _ptr(dct), _ptr(dequant_mf), n,
                                                                   _ptr(nz), _stream()), "optimize_chroma_dc_batch")
     return nz
 
 
-def denoise_dct_batch(dct, size, sums, offset):
+def denoise_dct_batch(dct, size, sums, offset, n=None):
     bd = _coef_bd(dct)
-    _rc(getattr(lib(), f"x264hip_{bd}_denoise_dct_batch")(_ptr(dct), size, dct.numel() // size, _ptr(sums),
+    _rc(getattr(lib(), f"x264hip_{bd}_denoise_dct_batch")(_ptr(dct), size, dct.numel() // size if n is None else n, _ptr(sums),
                                                            _ptr(offset), _stream()), "denoise_dct_batch")
     return dct
 
 
-def coef_stat_batch(kind, dct, pitch, n):
+def coef_stat_batch(kind, dct, pitch, n, out=None):
     import torch
     bd = _coef_bd(dct)
-    out = torch.empty(n, dtype=torch.int32, device=dct.device)
+    if out is None:
+        out = torch.empty(n, dtype=torch.int32, device=dct.device)
     _rc(getattr(lib(), f"x264hip_{bd}_coef_stat_batch")(kind, _ptr(dct), pitch, n, _ptr(out), _stream()),
         "coef_stat_batch")
     return out
 
 
-def coeff_level_run_batch(num, dct, pitch, n):
-    """returns (last, mask, count, level [n, 18])"""
+def coeff_level_run_batch(num, dct, pitch, n, outs=None):
+    """returns (last, mask, count, level [n, 18]) (outs = the four, or allocated: level zeroed)"""
     import torch
     bd = _coef_bd(dct)
-    last, mask, count = (torch.empty(n, dtype=torch.int32, device=dct.device) for _ in range(3))
-    level = torch.zeros((n, 18), dtype=dct.dtype, device=dct.device)
+    if outs is not None:
+        last, mask, count, level = outs
+    else:
+        last, mask, count = (torch.empty(n, dtype=torch.int32, device=dct.device) for _ in range(3))
+        level = torch.zeros((n, 18), dtype=dct.dtype, device=dct.device)
     _rc(getattr(lib(), f"x264hip_{bd}_coeff_level_run_batch")(num, _ptr(dct), pitch, n, _ptr(last), _ptr(mask),
                                                                _ptr(count), _ptr(level), _stream()),
         "coeff_level_run_batch")
     return last, mask, count, level
 
 
-def zigzag_scan_batch(size, field, dct):
+def zigzag_scan_batch(size, field, dct, level=None, n=None):
     import torch
     bd = _coef_bd(dct)
-    n = dct.numel() // (size * size)
-    level = torch.empty_like(dct)
+    if n is None:
+        n = dct.numel() // (size * size)
+    if level is None:
+        level = torch.empty_like(dct)
     _rc(getattr(lib(), f"x264hip_{bd}_zigzag_scan_batch")(size, int(field), _ptr(level), _ptr(dct), n, _stream()),
         "zigzag_scan_batch")
     return level
 
 
-def zigzag_sub_batch(kind, field, src, src_stride, dst, dst_stride, src_off, dst_off):
-    """returns (level [n, 16|64], dc [n], nz [n]); dst blocks become the src blocks."""
+def zigzag_sub_batch(kind, field, src, src_stride, dst, dst_stride, src_off, dst_off, outs=None):
+    """returns (level [n, 16|64], dc [n], nz [n]) (outs = the three, or allocated: dc zeroed); dst
+    blocks become the src blocks."""
     import torch
     bd = _pix_bd(src)
     n = src_off.numel()
     w = 8 if kind == 2 else 4
     ct = torch.int16 if bd == 8 else torch.int32
-    level = torch.empty((n, w * w), dtype=ct, device=src.device)
-    dc = torch.zeros(n, dtype=ct, device=src.device)
-    nz = torch.empty(n, dtype=torch.int32, device=src.device)
+    if outs is not None:
+        level, dc, nz = outs
+    else:
+        level = torch.empty((n, w * w), dtype=ct, device=src.device)
+        dc = torch.zeros(n, dtype=ct, device=src.device)
+        nz = torch.empty(n, dtype=torch.int32, device=src.device)
     _rc(getattr(lib(), f"x264hip_{bd}_zigzag_sub_batch")(kind, int(field), _ptr(level), _ptr(dc), _ptr(src),
                                                           src_stride, _ptr(dst), dst_stride, _ptr(src_off),
                                                           _ptr(dst_off), n, _ptr(nz), _stream()), "zigzag_sub_batch")
     return level, dc, nz
 
 
-def zigzag_interleave_batch(src):
+def zigzag_interleave_batch(src, outs=None, n=None):
     import torch
     bd = _coef_bd(src)
-    n = src.numel() // 64
-    dst = torch.empty_like(src)
-    nnz = torch.zeros((n, 16), dtype=torch.uint8, device=src.device)
+    if n is None:
+        n = src.numel() // 64
+    if outs is not None:
+        dst, nnz = outs
+    else:
+        dst = torch.empty_like(src)
+        nnz = torch.zeros((n, 16), dtype=torch.uint8, device=src.device)
     _rc(getattr(lib(), f"x264hip_{bd}_zigzag_interleave_batch")(_ptr(dst), _ptr(src), _ptr(nnz), n, _stream()),
         "zigzag_interleave_batch")
     return dst, nnz
@@ -712,20 +734,22 @@ def mb_dequant_idct_add(transform, dct, mb_width, mb_height, nframes, dequant_mf
     return recon
 
 
-def frame_init_lowres(planes, origin, stride, width, height, outs=None):
+def frame_init_lowres(planes, origin, stride, width, height, outs=None, lowres_stride=None, out_origin=None):
     """x264_frame_init_lowres of every frame of `planes` [n, rows, stride]: four half-resolution
-    planes [n, height/2 + 2*PAD, lowres_stride] with (0,0) at (PAD, PAD); returns (outs, lowres_stride)."""
+    planes [n, height/2 + 2*PAD, lowres_stride] with (0,0) at (PAD, PAD); returns (outs, lowres_stride).
+    With outs, lowres_stride / out_origin give their row stride and the element of (0,0) in each frame."""
     import torch
     bd = _pix_bd(planes)
     n = planes.shape[0]
     wl, hl = width // 2, height // 2
-    ls = plane_stride(wl)
+    ls = plane_stride(wl) if lowres_stride is None else lowres_stride
+    oo = PAD * ls + PAD if out_origin is None else out_origin
     if outs is None:
         # one buffer, the four planes equally spaced as x264's buffer_lowres (frame.c), which the
         # lookahead kernels address by plane index
         buf = torch.zeros((4, n, hl + 2 * PAD, ls), dtype=planes.dtype, device=planes.device)
         outs = [buf[k] for k in range(4)]
-    ptrs = (_P * 4)(*[o.data_ptr() + (PAD * ls + PAD) * o.element_size() for o in outs])
+    ptrs = (_P * 4)(*[o.data_ptr() + oo * o.element_size() for o in outs])
     _rc(getattr(lib(), f"x264hip_{bd}_frame_init_lowres")(
         _ptr(planes, origin), stride, planes[0].numel(), width, height, n, ptrs, ls, outs[0][0].numel(), _stream()),
         "frame_init_lowres")
@@ -762,7 +786,7 @@ def lowres_intra_cost(lowres, lowres_stride, mb_width, mb_height, satd=True, all
         rows = torch.empty((n, mb_height), dtype=torch.int32, device=dev) if with_rows else None
         est = torch.empty((n, 2), dtype=torch.int32, device=dev) if with_rows else None
     _rc(getattr(lib(), f"x264hip_{bd}_lowres_intra_cost")(
-        _ptr(lowres, PAD * lowres_stride + PAD), lowres_stride, lowres[0].numel(), mb_width, mb_height, n,
+        _ptr(lowres, PAD * lowres_stride + PAD), lowres_stride, _frame_stride(lowres), mb_width, mb_height, n,
         int(bool(satd)), int(bool(all_modes)), lam, _ptr(inv_qscale) if inv_qscale is not None else None,
         _ptr(cost), _ptr(rows) if rows is not None else None, _ptr(est) if est is not None else None,
         _stream()), "lowres_intra_cost")
@@ -895,12 +919,13 @@ def _plane_ptr(t, origin):
     return None if t is None else _ptr(t, origin)
 
 
-def ssim_wxh(pix1, origin1, stride1, pix2, origin2, stride2, width, height):
+def ssim_wxh(pix1, origin1, stride1, pix2, origin2, stride2, width, height, out=None):
     """x264_pixel_ssim_wxh (x264hip_*_ssim_wxh): (ssim float, cnt); planes with the region's
-    top-left at element origin1 / origin2"""
+    top-left at element origin1 / origin2; out: a float32 device tensor [1] for the sum"""
     import torch
     bd = _pix_bd(pix1)
-    out = torch.empty(1, dtype=torch.float32, device=pix1.device)
+    if out is None:
+        out = torch.empty(1, dtype=torch.float32, device=pix1.device)
     cnt = _c.c_int(0)
     f = getattr(lib(), f"x264hip_{bd}_ssim_wxh")
     _rc(f(_ptr(pix1, origin1), stride1, _ptr(pix2, origin2), stride2, width, height, _ptr(out), _c.byref(cnt),

@@ -141,6 +141,13 @@ __global__ __launch_bounds__( 256 ) void me_full_sad16_kernel( const typename PT
     }
     const typename PT<BD>::pixel *rb = ref + f * rfs + (intptr_t)(16 * mby + oy) * rs + 16 * mbx + ox + col;
     typename PT<BD>::sadt *out = table + mb * (W * P) + col;
+    // the padding entries of every row (un-centred tables: P - NCOL of them) are part of the
+    // table: zeros, from the last column's lane
+    if constexpr( P > NCOL )
+        if( col == NCOL - 1 )
+            for( int c = 0; c < W; c++ )
+                for( int k = 1; k <= P - NCOL; k++ )
+                    out[c * P + k] = 0;
 
     uint32_t acc[16];
     me_rows<BD, R, P>( rb, rs, F, acc, out, std::make_integer_sequence<int, 2 * R + 16>{} );
@@ -657,6 +664,19 @@ __global__ __launch_bounds__( 256 ) void me_full_sad16_v5_kernel( const uint16_t
     const uint32_t *rbase = (const uint32_t *)(ref + l.f * rfs + (intptr_t)(16 * l.mby + 8 * l.h + oy) * rs +
                                                16 * l.mbx + ox + 2 * l.grp);
     uint32_t *out = table + l.mb * ((2 * R + 1) * P) + 2 * l.grp;
+    // un-centred tables: the G pairs cover columns [0, 2R + 2) of the pitch's 2R + 4; the last
+    // pair of every row is padding no lane computes, and part of the table: zeroed ahead of
+    // the walk, row c by the MB's lane 2 * grp + h = c (the MB has 2R + 2 lanes for its 2R + 1
+    // rows: one store instruction per wave).  The 8 more bytes per 136-byte row cost 0.59 ->
+    // 0.63 ms per 16 1080p pairs wherever they are stored: from the last pair's two lanes ahead
+    // of the walk 0.64, in the row's own store step behind a branch 0.67, as a second store
+    // from every lane 0.63 (profiles/r10_table_padding_ab.log).
+    if constexpr( P > 2 * G )
+    {
+        const int c = 2 * l.grp + l.h;
+        if( c <= 2 * R )
+            *(uint2 *)(table + l.mb * ((2 * R + 1) * P) + c * P + 2 * G) = make_uint2( 0u, 0u );
+    }
     // both lanes of the pair hold the sums and both store them (to the same address): with
     // the store predicated on h == 0 the compiler kept every row's sums live across the
     // branch -- 220 VGPRs and 2 waves per SIMD instead of 118 and 4, the round-4 regression
@@ -686,6 +706,17 @@ __global__ __launch_bounds__( 256 ) void me_full_sad8q_v5_kernel( const uint16_t
     // quadrants 2h (left) and 2h + 1 (right), columns 2g, 2g+1 as one dword each
     uint32_t *ql = (uint32_t *)(table8 + (l.mb * 4 + 2 * l.h) * ((2 * R + 1) * P) + 2 * l.grp);
     uint32_t *qr = ql + (2 * R + 1) * P / 2;
+    // the pitch's last column pair (2R + 2, 2R + 3) is padding no lane computes: zeros, ahead
+    // of the walk, rows grp and grp + G of the lane's two quadrants (G lanes per half for the
+    // 2R + 1 = 2G - 1 rows): 0.66 -> 0.76 ms per 16 1080p pairs; from the last pair's lanes
+    // alone 0.83, in the row's own step 0.79 (branch) and 0.83 (every lane)
+    // (profiles/r10_table_padding_ab.log)
+    static_assert( P == 2 * G + 2, "one padding dword per row" );
+    for( int c = l.grp; c <= 2 * R; c += G )
+    {
+        ql[c * (P / 2) + G - l.grp] = 0u;
+        qr[c * (P / 2) + G - l.grp] = 0u;
+    }
     auto store = [ql, qr]( int c, uint32_t left, uint32_t right ) {
         ql[c * (P / 2)] = left;
         qr[c * (P / 2)] = right;
@@ -1168,8 +1199,8 @@ X264HIP_INSTANTIATE( launch_me_search_esa );
 // fixed, so their cost_mv terms are read once; the row term once per step.  Each entry's
 // key (cost << 12 | raster index in the clipped, width-rounded window) is built as
 // sat( sat( (sad << 12) + C[k] ) + S ) with C[k] = all ones outside the window or the table's
-// columns, so whatever such an entry holds (a full 10-bit table's padding columns are never
-// written) its key saturates (valid keys stay below 392958 << 12 + 4096), a wave min picks the lowest cost and, among equal costs, the first in raster
+// columns, so whatever such an entry holds (the SADs of mx > R, or zeros) its key saturates
+// (valid keys stay below 392958 << 12 + 4096), a wave min picks the lowest cost and, among equal costs, the first in raster
 // order -- what the strict-< scan of the reference keeps -- and it replaces the predictor
 // result only if strictly better (COPY3_IF_LT, me.h:87-93).
 // Table geometry: rows = 2R+1 at `pitch`, `cols` valid columns, window origin (ox, oy)
