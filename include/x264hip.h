@@ -585,9 +585,10 @@ int x264hip_##BD##_lowres_intra_cost( const pixel *lowres, intptr_t stride,     
  * fenc->lowres_mvs (mvs[2*(f*mbs + mb)]), lowres_mv_costs (mv_costs), lowres_costs               \
  * ((list_used << 14) + cost), the AQ-scaled inter row sums row_satd[f*mbh + y]                  \
  * (i_row_satds[b-p0][0]) and est[3f..3f+2] = cost_est, cost_est_aq, intra_mbs.                  \
- * inv_qscale NULL = AQ off; row_satd / est may be NULL.  Synchronous: the call waits            \
- * for the kernel and returns X264HIP_EDEVICE ("timed out", outputs invalid) if a band's         \
- * wait for the band below it ran out (a broken dispatch-order premise, never a normal run). */  \
+ * inv_qscale NULL = AQ off; row_satd / est may be NULL.  Asynchronous on `stream`, no host      \
+ * wait: if a band's wait for the band below it ran out (a broken dispatch-order premise,        \
+ * never a normal run; outputs invalid) x264hip_lowres_status( stream ), or the next lookahead   \
+ * entry after the failure has reached the host, returns X264HIP_EDEVICE ("timed out"). */       \
 int x264hip_##BD##_lowres_inter_cost( const pixel *fenc, intptr_t fenc_frame_stride,             \
                                       const pixel *ref_f, const pixel *ref_h,                     \
                                       const pixel *ref_v, const pixel *ref_c, intptr_t stride,   \

@@ -1562,7 +1562,7 @@ def _lap_call(hip, c, dev, tight):
     r = hip.lowres_inter_cost(c.lows[0].body(dev)[1:], [p.body(dev)[:-1] for p in c.lows], c.lows[0].stride, c.mbw, c.mbh,
                               T(c.intra, dev), (T(c.cm, dev), c.c0), outs=outs,
                               ref_w=None if c.refw is None else c.refw.body(dev)[:-1], weight=c.weight,
-                              n_slices=c.n_slices)
+                              n_slices=c.n_slices, check=getattr(c, "check", True))
     return dict(zip(("mvs", "mv_costs", "lowres_costs", "row_satd", "est"), r)) if tight else None
 
 
@@ -1599,7 +1599,7 @@ def _lab_call(hip, c, dev, tight):
                               c.mbh, (T(c.cm, dev), c.c0), c.search, T(c.mvs[0], dev), T(c.costs[0], dev),
                               T(c.mvs[1], dev), T(c.costs[1], dev), dist_scale_factor=128, bipred_weight=32,
                               outs=None if tight else (T(c.lc, dev), T(c.rows, dev), T(c.est, dev)),
-                              n_slices=c.n_slices)
+                              n_slices=c.n_slices, check=getattr(c, "check", True))
     if not tight:
         return None
     out = dict(zip(("lowres_costs", "row_satd", "est"), r))
@@ -1740,7 +1740,7 @@ def _ssim_setup(ar, bd, W, H):
 def _ssim_call(hip, c, dev, tight):
     import torch
     out = torch.empty(1, dtype=torch.float32, device="cuda") if tight else T(c.out, dev)
-    hip.ssim_wxh(c.a.t(dev), c.a.origin, c.a.stride, c.b.t(dev), c.b.origin, c.b.stride, c.W, c.H, out=out)
+    hip.ssim_wxh(c.a.t(dev), c.a.origin, c.a.stride, c.b.t(dev), c.b.origin, c.b.stride, c.W, c.H, out=out, wait=False)
     return {"ssim": out} if tight else None
 
 

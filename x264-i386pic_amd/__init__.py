@@ -919,9 +919,11 @@ def _plane_ptr(t, origin):
     return None if t is None else _ptr(t, origin)
 
 
-def ssim_wxh(pix1, origin1, stride1, pix2, origin2, stride2, width, height, out=None):
+def ssim_wxh(pix1, origin1, stride1, pix2, origin2, stride2, width, height, out=None, wait=True):
     """x264_pixel_ssim_wxh (x264hip_*_ssim_wxh): (ssim float, cnt); planes with the region's
-    top-left at element origin1 / origin2; out: a float32 device tensor [1] for the sum"""
+    top-left at element origin1 / origin2; out: a float32 device tensor [1] for the sum.  The
+    entry is asynchronous; reading the float waits for the current stream.  wait=False returns
+    (out, cnt) instead -- the device tensor, valid once the stream has passed the launch."""
     import torch
     bd = _pix_bd(pix1)
     if out is None:
@@ -930,7 +932,7 @@ def ssim_wxh(pix1, origin1, stride1, pix2, origin2, stride2, width, height, out=
     f = getattr(lib(), f"x264hip_{bd}_ssim_wxh")
     _rc(f(_ptr(pix1, origin1), stride1, _ptr(pix2, origin2), stride2, width, height, _ptr(out), _c.byref(cnt),
           _stream()), "ssim_wxh")
-    return float(out.item()), cnt.value
+    return (float(out.item()) if wait else out), cnt.value
 
 
 def ssim_encoder_bands(mb_height, height, slices=None):
