@@ -32,6 +32,7 @@ __all__ = [
     "me_search_ref_tesa", "me_refine_bidir", "me_refine_qpel_refdupe", "plane_upload", "upload_plane", "upload_planes",
     "mbtree_propagate", "mbtree_finish", "mbtree_plan", "mbtree_step", "MbtreeStep",
     "mb_mc", "Mc",
+    "deblock_strength", "deblock_frames", "chroma_qp_table", "Deblock", "DeblockStrength",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -336,7 +337,8 @@ def cqm_dequant(scaling_lists, transform_8x8=True):
 
 
 # ----------------------------------------------------------------- declarations
-# Every function of include/x264hip.h, include/x264hip_mbtree.h and include/x264hip_mc.h, once:
+# Every function of include/x264hip.h, include/x264hip_mbtree.h, include/x264hip_mc.h and
+# include/x264hip_deblock.h, once:
 # "return:parameters", one letter each, in the struct module's spelling where it has one.
 # tests/test_abi.py checks the first two tables against x264hip.h's prototypes,
 # tests/test_cpu_mbtree.py the third against x264hip_mbtree.h's, tests/test_cpu_mc.py the fourth
@@ -450,6 +452,14 @@ _MBTREE = {
 _MC = {
     "mb_mc": "i:PiPPPiP",
 }
+# include/x264hip_deblock.h: x264hip_8_<name> and x264hip_10_<name>, then x264hip_<name>
+# (tests/test_cpu_deblock.py checks both against the header's prototypes)
+_DEBLOCK = {
+    "deblock_frames": "i:PiiiP",
+}
+_DEBLOCK_PLAIN = {
+    "deblock_strength": "i:PiiiPP",
+}
 
 
 def _declare(L):
@@ -467,6 +477,11 @@ def _declare(L):
     for name, sig in _MC.items():
         for bd in (8, 10):
             declare(getattr(L, f"x264hip_{bd}_{name}"), sig)
+    for name, sig in _DEBLOCK.items():
+        for bd in (8, 10):
+            declare(getattr(L, f"x264hip_{bd}_{name}"), sig)
+    for name, sig in _DEBLOCK_PLAIN.items():
+        declare(getattr(L, f"x264hip_{name}"), sig)
 
 
 # ----------------------------------------------------------------- CQM
@@ -1250,6 +1265,91 @@ def mb_mc(planes0, planes1, ref_origin, ref_stride, i_pixel, pos, par, mode=None
     _rc(getattr(lib(), name)(_c.byref(m), i_pixel, *arrays, _ptr(mode) if mode is not None and n else None,
                              n, _stream()), name)
     return pred, pred_c
+
+
+# ----------------------------------------------------------------- deblocking (include/x264hip_deblock.h)
+class Deblock(_c.Structure):
+    """x264hip_deblock_t"""
+    _fields_ = [("chroma_format", _c.c_int32), ("alpha_c0_offset", _c.c_int32), ("beta_offset", _c.c_int32),
+                ("chroma_qp_index_offset", _c.c_int32), ("chroma_qp_table", _P), ("luma", _P), ("luma_stride", _IP),
+                ("luma_frame_stride", _IP), ("chroma", _P * 2), ("chroma_stride", _IP), ("chroma_frame_stride", _IP),
+                ("qp", _P), ("mb_flags", _P), ("bs", _P), ("slice_table", _P)]
+
+
+class DeblockStrength(_c.Structure):
+    """x264hip_deblock_strength_t"""
+    _fields_ = [("nz", _P), ("mb_flags", _P), ("mv", _P * 2), ("ref", _P * 2), ("bframe", _c.c_int32),
+                ("mvy_limit", _c.c_int32)]
+
+
+def chroma_qp_table(bitdepth, chroma_qp_index_offset=0):
+    """h->chroma_qp_table[0 .. QP_MAX_SPEC] as uint8: the chroma qp of every luma qp (H.264 table
+    8-15 shifted by QP_BD_OFFSET, the index offset applied and clipped first).  Pure host code."""
+    _check_bd(bitdepth)
+    bdo = 6 * (bitdepth - 8)
+    tail = [29, 30, 31, 32, 32, 33, 34, 34, 35, 35, 36, 36, 37, 37, 37, 38, 38, 38, 39, 39, 39, 39]
+    out = np.zeros(52 + bdo, np.uint8)
+    for qp in range(52 + bdo):
+        q = min(max(qp + chroma_qp_index_offset, 0), 51 + bdo)
+        out[qp] = q if q - bdo < 30 else tail[q - bdo - 30] + bdo
+    return out
+
+
+def deblock_strength(nz, mb_flags, mv0, ref0, mb_width, mb_height, nframes=1, mv1=None, ref1=None, mvy_limit=4,
+                     bs=None):
+    """bS of every edge segment of nframes frames (x264hip_deblock_strength): nz int32 [mbs] as
+    mb_dct_quant writes it, mb_flags uint8 [mbs] (bit 0 intra, bit 1 transform 8x8), mv0 int16
+    [nframes, 4*mbh, 4*mbw, 2] and ref0 int8 [nframes, 2*mbh, 2*mbw] (h->mb.mv[0] / h->mb.ref[0]);
+    mv1 / ref1 make it a B frame.  Returns bs uint8 [mbs, 2, 4, 4]."""
+    import torch
+    nmb = nframes * mb_width * mb_height
+    if bs is None:
+        bs = torch.empty((nmb, 2, 4, 4), dtype=torch.uint8, device=nz.device)
+    s = DeblockStrength()
+    s.nz, s.mb_flags = _ptr(nz).value, _ptr(mb_flags).value
+    s.mv[0], s.ref[0] = _ptr(mv0).value, _ptr(ref0).value
+    if mv1 is not None or ref1 is not None:
+        s.mv[1], s.ref[1], s.bframe = _ptr(mv1).value, _ptr(ref1).value, 1
+    s.mvy_limit = mvy_limit
+    _rc(lib().x264hip_deblock_strength(_c.byref(s), mb_width, mb_height, nframes, _ptr(bs), _stream()),
+        "deblock_strength")
+    return bs
+
+
+def deblock_frames(luma, origin, stride, mb_width, mb_height, qp, mb_flags, bs, chroma=None, alpha_c0_offset=0,
+                   beta_offset=0, chroma_qp_index_offset=0, qp_table=None, slice_table=None, nframes=None):
+    """x264_frame_deblock_row over whole frames, in place (x264hip_*_deblock_frames): luma
+    [nframes, rows, stride] with pixel (0,0) at element `origin`; qp int8, mb_flags uint8 (bit 0
+    intra, bit 1 transform 8x8, bit 2 partition == D_16x16 && !cbp) [mbs]; bs uint8 [mbs, 2, 4, 4].
+    chroma = (chroma_format, planes, chroma_origin, chroma_stride) with planes = [NV12 / NV16
+    tensor] (4:2:0 / 4:2:2) or [U, V] (4:4:4); None = luma only.  qp_table: h->chroma_qp_table
+    (host uint8 array), default chroma_qp_table(depth, chroma_qp_index_offset).  slice_table int32
+    [mbs] or None (edges between slices are filtered).  Returns (luma, chroma planes)."""
+    bd = _pix_bd(luma)
+    cf, planes, c_origin, c_stride = chroma if chroma is not None else (0, (), 0, 0)
+    planes = list(planes or ())
+    n = (luma.shape[0] if luma.dim() == 3 else 1) if nframes is None else nframes
+    table = chroma_qp_table(bd, chroma_qp_index_offset) if qp_table is None else \
+        np.ascontiguousarray(np.asarray(qp_table, np.uint8))
+    if table.size < 52 + 6 * (bd - 8):
+        raise ValueError("deblock_frames: the chroma qp table needs QP_MAX_SPEC + 1 entries")
+    d = Deblock()
+    d.chroma_format, d.alpha_c0_offset, d.beta_offset = int(cf), int(alpha_c0_offset), int(beta_offset)
+    d.chroma_qp_index_offset = int(chroma_qp_index_offset)
+    d.chroma_qp_table = table.ctypes.data
+    d.luma, d.luma_stride = _ptr(luma, origin).value, stride
+    d.luma_frame_stride = _frame_stride(luma) if luma.dim() == 3 else 0
+    for k, t in enumerate(planes):
+        d.chroma[k] = _ptr(t, c_origin).value
+    if planes:
+        d.chroma_stride = c_stride
+        d.chroma_frame_stride = _frame_stride(*planes) if planes[0].dim() == 3 else 0
+    d.qp, d.mb_flags, d.bs = _ptr(qp).value, _ptr(mb_flags).value, _ptr(bs).value
+    if slice_table is not None:
+        d.slice_table = _ptr(slice_table).value
+    name = f"x264hip_{bd}_deblock_frames"
+    _rc(getattr(lib(), name)(_c.byref(d), mb_width, mb_height, n, _stream()), name)
+    return luma, planes
 
 
 def plane_stride(width, pad=PAD):

@@ -12,6 +12,7 @@
 #include "x264hip.h"
 #include "x264hip_mbtree.h"
 #include "x264hip_mc.h"
+#include "x264hip_deblock.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -1626,6 +1627,62 @@ extern "C" int x264hip_10_mb_mc( const x264hip_mc_t *mc, int i_pixel, const int3
                                  const int32_t *mode, int n, void *stream )
 {
     return mb_mc_entry<10>( mc, i_pixel, pos, par, mode, n, stream );
+}
+
+// ------------------------------------------------------------ deblocking (x264hip_deblock.h)
+// every argument error is X264HIP_EINVAL before any HIP call; of the pointers only d and
+// d->chroma_qp_table (host memory) are dereferenced
+template <int BD>
+static int deblock_frames_entry( const x264hip_deblock_t *d, int mb_width, int mb_height, int n_frames, void *stream )
+{
+    if( !d || mb_width < 0 || mb_height < 0 || n_frames < 0 )
+        return X264HIP_EINVAL;
+    const int cf = d->chroma_format;
+    if( cf < 0 || cf > 3 || !d->luma || !d->qp || !d->mb_flags || !d->bs || !d->chroma_qp_table ||
+        ( cf && !d->chroma[0] ) || ( cf == 3 && !d->chroma[1] ) )
+        return X264HIP_EINVAL;
+    if( d->alpha_c0_offset < -12 || d->alpha_c0_offset > 12 || d->beta_offset < -12 || d->beta_offset > 12 )
+        return X264HIP_EINVAL;
+    const int64_t mbs = (int64_t)n_frames * mb_width * mb_height;
+    if( mbs > ( 1 << 28 ) )
+        return X264HIP_EINVAL;
+    if( mbs == 0 )
+        return X264HIP_OK;
+    if( int rc = any_device() )
+        return rc;
+    return map_err( launch_deblock_frames<BD>( d, mb_width, mb_height, n_frames, (hipStream_t)stream ),
+                    "deblock_frames" );
+}
+
+extern "C" int x264hip_8_deblock_frames( const x264hip_deblock_t *d, int mb_width, int mb_height, int n_frames,
+                                         void *stream )
+{
+    return deblock_frames_entry<8>( d, mb_width, mb_height, n_frames, stream );
+}
+
+extern "C" int x264hip_10_deblock_frames( const x264hip_deblock_t *d, int mb_width, int mb_height, int n_frames,
+                                          void *stream )
+{
+    return deblock_frames_entry<10>( d, mb_width, mb_height, n_frames, stream );
+}
+
+extern "C" int x264hip_deblock_strength( const x264hip_deblock_strength_t *s, int mb_width, int mb_height,
+                                         int n_frames, uint8_t *bs, void *stream )
+{
+    if( !s || !bs || mb_width < 0 || mb_height < 0 || n_frames < 0 )
+        return X264HIP_EINVAL;
+    if( !s->nz || !s->mb_flags || !s->mv[0] || !s->ref[0] || ( s->bframe && ( !s->mv[1] || !s->ref[1] ) ) ||
+        s->mvy_limit < 1 )
+        return X264HIP_EINVAL;
+    const int64_t mbs = (int64_t)n_frames * mb_width * mb_height;
+    if( mbs > ( 1 << 28 ) )
+        return X264HIP_EINVAL;
+    if( mbs == 0 )
+        return X264HIP_OK;
+    if( int rc = any_device() )
+        return rc;
+    return map_err( launch_deblock_strength( s, mb_width, mb_height, n_frames, bs, (hipStream_t)stream ),
+                    "deblock_strength" );
 }
 
 // dequant4_mf / dequant8_mf of x264_cqm_init, reference common/set.c:31-39,

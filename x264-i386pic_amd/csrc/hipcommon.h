@@ -704,3 +704,13 @@ template <int BD>
 hipError_t launch_mb_mc( const x264hip_mc_t *mc, int i_pixel, const int32_t *pos, const int16_t *par,
                          const int32_t *mode, int n, hipStream_t stream );
 } // namespace x264hip
+
+// the deblocking filter (deblock.hip; include/x264hip_deblock.h)
+struct x264hip_deblock_t;
+struct x264hip_deblock_strength_t;
+namespace x264hip {
+template <int BD>
+hipError_t launch_deblock_frames( const x264hip_deblock_t *d, int mbw, int mbh, int n_frames, hipStream_t stream );
+hipError_t launch_deblock_strength( const x264hip_deblock_strength_t *s, int mbw, int mbh, int n_frames, uint8_t *bs,
+                                    hipStream_t stream );
+} // namespace x264hip
