@@ -82,11 +82,11 @@ def test_hpel_ref_tables():
         want = ref_array("x264_hpel_ref%d" % k)
         assert len(want) == 16
         assert c_array(ORACLE, "hpel_ref%d" % k) == want
-        assert c_array(os.path.join(CSRC, "lookahead.hip"), "c_lr_ref%d" % k) == want
+        assert c_array(os.path.join(CSRC, "mcdev.h"), "c_ref%d" % k) == want
 
 
 def test_me_pattern_tables():
-    la = os.path.join(CSRC, "lookahead.hip")
+    la = os.path.join(CSRC, "hipcommon.h")
     for ref_name, orc_name, hip_name, n in (("mod6m1", "lr_mod6m1", "c_mod6m1", 8),
                                            ("hex2", "lr_hex2", "c_hex2", 16),
                                            ("square1", "lr_square1", "c_square1", 18)):
@@ -94,6 +94,46 @@ def test_me_pattern_tables():
         assert len(want) == n
         assert c_array(ORACLE, orc_name) == want, orc_name
         assert c_array(la, hip_name) == want, hip_name
+
+
+def brace_lists(path):
+    """Integers of every brace initialiser of a file that holds numbers only (comments
+    stripped; nested groups flattened, each inner group also on its own)."""
+    src = _text(path)
+    out = []
+    for m in re.finditer(r"\{", src):
+        depth, j = 0, m.start()
+        while j < len(src):
+            if src[j] == "{":
+                depth += 1
+            elif src[j] == "}":
+                depth -= 1
+                if depth == 0:
+                    break
+            j += 1
+        body = src[m.start():j + 1]
+        if re.fullmatch(r"[\s\d,{}+-]*", body):
+            out.append([int(v) for v in re.findall(r"-?\d+", body)])
+    return out
+
+
+def test_single_copies_of_small_tables():
+    """The hpel_ref tables live in csrc/mcdev.h and the search patterns in csrc/hipcommon.h, once:
+    no other file under csrc/ restates one of them as a brace initialiser."""
+    owner = {"x264_hpel_ref0": "mcdev.h", "x264_hpel_ref1": "mcdev.h", "hex2": "hipcommon.h",
+             "mod6m1": "hipcommon.h", "square1": "hipcommon.h"}
+    want = {name: ref_array(name) for name in owner}
+    seen = {name: 0 for name in owner}
+    for fn in sorted(os.listdir(CSRC)):
+        path = os.path.join(CSRC, fn)
+        if not os.path.isfile(path) or not fn.endswith((".hip", ".h", ".cpp", ".inc")):
+            continue
+        for lst in brace_lists(path):
+            for name, w in want.items():
+                if lst == w:
+                    assert fn == owner[name], (fn, name)
+                    seen[name] += 1
+    assert all(n == 1 for n in seen.values()), seen
 
 
 def test_zigzag_scans():

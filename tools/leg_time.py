@@ -4,17 +4,33 @@ PMC passes and A/Bs): leg_time.py LEG [steps] [pairs] with LEG one of esa (the E
 fused legs), refine (refine_subpel with chroma ME on the quarter-pel sequence), full8 (the quadrant tables),
 tesa, la (the lookahead's P and B searches), wp (the weight search), me10 (configs[4]'s 10-bit
 full search, quadrant tables and 8x8 DCT+quant), esa8 (the sub-partition ESA decisions beside the
-quadrant tables).  Prints the legs' JSON."""
+quadrant tables), bidir (the bipred refine alone) and search (x264_me_search_ref alone), both on
+rates_refine's quarter-pel sequence.  Prints the legs' JSON."""
 import json
 import os
 import sys
 import types
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
+
+
+def subpel_inputs(x, mbw, mbh, F):
+    """rates_refine's inputs: the quarter-pel sequence, its half-pel planes, chroma and mv costs"""
+    from x264hip import synth
+    luma, stride, origin, nv, cs, co = synth.make_subpel_sequence(F + 1, mbw * 16, mbh * 16, 8, start=0)
+    dev = torch.from_numpy(luma).cuda()
+    nvd = torch.from_numpy(nv).cuda()
+    _, _, cm, span = bench.tesa_params(mbw, mbh, F, 16, centre=(0, 0))
+    cm_d = torch.from_numpy(cm.view(np.int16)).cuda()
+    planes = [dev[:-1]] + list(x.hpel_filter(dev[:-1], origin, stride, mbw * 16, mbh * 16))
+    ext = x.refine_ext(1, 1, 0, fenc_chroma=[nvd[1:]], fenc_chroma_origin=co, fenc_chroma_stride=cs,
+                       ref_chroma=[nvd[:-1]], ref_chroma_origin=co, ref_chroma_stride=cs)
+    return dev, stride, origin, luma[0].size, planes, ext, cm, cm_d, span
 
 
 def main():
@@ -50,6 +66,12 @@ def main():
     elif leg == "wp":
         res = bench.rates_weightp(x, a, 1, dev, origin, stride, mbw, mbh)
         res.update(bench.rates_ssim(x, a, 1, dev, origin, stride, mbw, mbh))
+    elif leg in ("bidir", "search"):
+        sdev, sstride, sorigin, sfs, splanes, ext, cm, cm_d, span = subpel_inputs(x, mbw, mbh, F)
+        if leg == "bidir":
+            res = bench.rates_bidir(x, a, 1, mbw, mbh, F - 1, sdev, sstride, sorigin, sfs, splanes, cm_d, span)
+        else:
+            res = bench.rates_search(x, a, 1, mbw, mbh, F, sdev, sstride, sorigin, sfs, splanes, ext, cm, cm_d, span)
     else:
         raise SystemExit("unknown leg %s" % leg)
     print(json.dumps(res))

@@ -19,6 +19,31 @@ template <int N> constexpr uint32_t pack_fields( const uint8_t ( &a )[N], int b 
     return r;
 }
 __device__ __forceinline__ int field( uint32_t k, int b, int i ) { return (int)((k >> (b * i)) & ((1u << b) - 1)); }
+// signed (x, y) entries, component c biased by `bias`, as bit fields
+template <int N> constexpr uint32_t pack_fields_s( const int8_t ( &a )[N][2], int c, int b, int bias )
+{
+    uint32_t r = 0;
+    for( int i = 0; i < N; i++ )
+        r |= (uint32_t)(a[i][c] + bias) << (b * i);
+    return r;
+}
+
+// The reference's small search-pattern tables (me.c:53-56; pinned to the reference text by
+// tests/test_ref_tables.py): the only copies.  The searches index them with per-lane values on
+// their serial chain, so they are read as bit fields of compile-time words, never as memory: a
+// table load was one more dependent memory round per hexagon step.
+constexpr int8_t c_hex2[8][2] = { { -1, -2 }, { -2, 0 }, { -1, 2 }, { 1, 2 }, { 2, 0 }, { 1, -2 }, { -1, -2 }, { -2, 0 } };
+constexpr uint8_t c_mod6m1[8] = { 5, 0, 1, 2, 3, 4, 5, 0 };
+constexpr int8_t c_square1[9][2] = { { 0, 0 }, { 0, -1 }, { 0, 1 }, { -1, 0 }, { 1, 0 },
+                                     { -1, -1 }, { -1, 1 }, { 1, -1 }, { 1, 1 } };
+constexpr uint32_t k_hex2_x = pack_fields_s( c_hex2, 0, 3, 2 ), k_hex2_y = pack_fields_s( c_hex2, 1, 3, 2 );
+constexpr uint32_t k_mod6m1_w = pack_fields( c_mod6m1, 3 );
+constexpr uint32_t k_square1_x = pack_fields_s( c_square1, 0, 2, 1 ), k_square1_y = pack_fields_s( c_square1, 1, 2, 1 );
+__device__ __forceinline__ int hex2_x( int j ) { return field( k_hex2_x, 3, j ) - 2; }
+__device__ __forceinline__ int hex2_y( int j ) { return field( k_hex2_y, 3, j ) - 2; }
+__device__ __forceinline__ int mod6m1( int j ) { return field( k_mod6m1_w, 3, j ); }
+__device__ __forceinline__ int square1_x( int k ) { return field( k_square1_x, 2, k ) - 1; }
+__device__ __forceinline__ int square1_y( int k ) { return field( k_square1_y, 2, k ) - 1; }
 
 template <int BD> struct PT;
 template <> struct PT<8>
@@ -300,43 +325,6 @@ __device__ __forceinline__ int shr_clip( int v )
 template <int BD> __device__ __forceinline__ int upix( uint32_t w, int k )
 {
     return BD == 8 ? (int)((w >> (8 * k)) & 0xff) : (int)((w >> (16 * k)) & 0xffff);
-}
-
-// ---- motion compensation pieces shared by the subpel refine (refine.hip) and x264_mb_mc (mbmc.hip) ----
-// get_ref's plane pair per qpel phase (mc.c:203-209, common/tables.c:183-184)
-constexpr uint8_t c_ref0[16] = { 0, 1, 1, 1, 0, 1, 1, 1, 2, 3, 3, 3, 0, 1, 1, 1 };   // x264_hpel_ref0
-constexpr uint8_t c_ref1[16] = { 0, 0, 1, 0, 2, 2, 3, 2, 2, 2, 3, 2, 2, 2, 3, 2 };   // x264_hpel_ref1
-
-// explicit weight of one plane (x264_weight_t, mc.c:117-137): rnd = 1 << (denom - 1) or 0,
-// offset already scaled by 1 << (BIT_DEPTH - 8)
-struct RsWeight
-{
-    int on, scale, denom, rnd, offset;
-};
-
-// mc_weight of packed pixels: clip( ((v * scale + rnd) >> denom) + offset ) per pixel
-template <int BD> __device__ __forceinline__ uint32_t weigh_packed( uint32_t w, const RsWeight &wt )
-{
-    constexpr int PPD = PT<BD>::PPD, SH = 32 / PPD;
-    uint32_t r = 0;
-#pragma unroll
-    for( int k = 0; k < PPD; k++ )
-    {
-        const int v = upix<BD>( w, k );
-        r |= (uint32_t)clip_pix<BD>( ((v * wt.scale + wt.rnd) >> wt.denom) + wt.offset ) << (SH * k);
-    }
-    return r;
-}
-
-// the (U, V) samples of pixel x of a row of interleaved (NV12 / NV16) words, as u16 lanes
-typedef unsigned short rs_us2 __attribute__( ( ext_vector_type( 2 ) ) );
-__device__ __forceinline__ rs_us2 as_us2( uint32_t v ) { return __builtin_bit_cast( rs_us2, v ); }
-template <int BD> __device__ __forceinline__ rs_us2 nv_pair( const uint32_t *w, int x )
-{
-    if constexpr( BD == 8 )
-        return as_us2( __builtin_amdgcn_perm( 0u, w[x >> 1], (x & 1) ? 0x0c030c02u : 0x0c010c00u ) );
-    else
-        return as_us2( w[x] );
 }
 
 } // namespace x264hip

@@ -18,38 +18,9 @@
 // refinement) with fenc rows held in registers, integer patterns scored from a
 // register window of the F plane and get_ref rebuilt from the four lowres
 // planes; the frame pairs of a batch run in parallel.
-#include "hipcommon.h"
+#include "mcdev.h"
 
 namespace x264hip {
-
-// The reference's small tables (tables.c hpel_ref0/1, me.c mod6m1/hex2/square1; pinned to the
-// reference text by tests/test_ref_tables.py).  The searches index them with per-lane values
-// on their serial chain, so the kernels read them as bit fields of compile-time words
-// (an immediate shift and mask) rather than as memory: a table load was one more dependent
-// memory round per hexagon step and per get_ref.
-constexpr uint8_t c_lr_ref0[16] = { 0, 1, 1, 1, 0, 1, 1, 1, 2, 3, 3, 3, 0, 1, 1, 1 };   // x264_hpel_ref0
-constexpr uint8_t c_lr_ref1[16] = { 0, 0, 1, 0, 2, 2, 3, 2, 2, 2, 3, 2, 2, 2, 3, 2 };   // x264_hpel_ref1
-constexpr int8_t c_hex2[8][2] = { { -1, -2 }, { -2, 0 }, { -1, 2 }, { 1, 2 }, { 2, 0 }, { 1, -2 }, { -1, -2 }, { -2, 0 } };
-constexpr uint8_t c_mod6m1[8] = { 5, 0, 1, 2, 3, 4, 5, 0 };
-constexpr int8_t c_square1[9][2] = { { 0, 0 }, { 0, -1 }, { 0, 1 }, { -1, 0 }, { 1, 0 },
-                                     { -1, -1 }, { -1, 1 }, { 1, -1 }, { 1, 1 } };
-// signed entries biased by `bias`, as bit fields (pack_fields)
-template <int N> constexpr uint32_t lr_pack_s( const int8_t ( &a )[N][2], int c, int b, int bias )
-{
-    uint32_t r = 0;
-    for( int i = 0; i < N; i++ )
-        r |= (uint32_t)(a[i][c] + bias) << (b * i);
-    return r;
-}
-constexpr uint32_t k_lr_ref0 = pack_fields( c_lr_ref0, 2 ), k_lr_ref1 = pack_fields( c_lr_ref1, 2 );
-constexpr uint32_t k_hex2_x = lr_pack_s( c_hex2, 0, 3, 2 ), k_hex2_y = lr_pack_s( c_hex2, 1, 3, 2 );
-constexpr uint32_t k_mod6m1 = pack_fields( c_mod6m1, 3 );
-constexpr uint32_t k_square1_x = lr_pack_s( c_square1, 0, 2, 1 ), k_square1_y = lr_pack_s( c_square1, 1, 2, 1 );
-__device__ __forceinline__ int lr_hex2_x( int j ) { return (int)((k_hex2_x >> (3 * j)) & 7) - 2; }
-__device__ __forceinline__ int lr_hex2_y( int j ) { return (int)((k_hex2_y >> (3 * j)) & 7) - 2; }
-__device__ __forceinline__ int lr_mod6m1( int j ) { return (int)((k_mod6m1 >> (3 * j)) & 7); }
-__device__ __forceinline__ int lr_square1_x( int k ) { return (int)((k_square1_x >> (2 * k)) & 3) - 1; }
-__device__ __forceinline__ int lr_square1_y( int k ) { return (int)((k_square1_y >> (2 * k)) & 3) - 1; }
 
 constexpr int LR_COST_MAX = 1 << 28;
 
@@ -287,12 +258,9 @@ template <int BD> struct LrCtx
 #pragma unroll
         for( int n = 0; n < N; n++ )
         {
-            const int idx = ((my[n] & 3) << 2) + (mx[n] & 3);
-            const intptr_t off = (intptr_t)(my[n] >> 2) * stride + (mx[n] >> 2);
-            const int i0 = (int)((k_lr_ref0 >> (2 * idx)) & 3), i1 = (int)((k_lr_ref1 >> (2 * idx)) & 3);
             // (the plane by one multiply-add: the four planes equally spaced)
-            const pixel *s1 = p0 + i0 * pd + off + ((my[n] & 3) == 3) * stride;
-            const pixel *s2 = (idx & 5) ? p0 + i1 * pd + off + ((mx[n] & 3) == 3) : s1;
+            const RefPhase ph = ref_phase( mx[n], my[n], stride );
+            const pixel *s1 = ref_ptr0( ph, p0, pd, stride ), *s2 = ph.two() ? ref_ptr1( ph, p0, pd ) : s1;
 #pragma unroll
             for( int y = 0; y < LR_NR; y++ )
             {
@@ -585,8 +553,8 @@ __device__ void lr_me_search( const LrCtx<BD> &m, int mvpx, int mvpy, const int 
         if( bcost & 7 )
         {
             int dir = (bcost & 7) - 2;
-            bmx += lr_hex2_x( dir + 1 );
-            bmy += lr_hex2_y( dir + 1 );
+            bmx += hex2_x( dir + 1 );
+            bmy += hex2_y( dir + 1 );
             for( int i = (me_range >> 1) - 1; i > 0 && m.in_range( bmx, bmy ); i-- )
             {
                 // the window scores all six hexagon points (c_hex2[0..5] order); the three
@@ -601,7 +569,7 @@ __device__ void lr_me_search( const LrCtx<BD> &m, int mvpx, int mvpy, const int 
                 };
 #pragma unroll
                 for( int k = 0; k < 3; k++ )
-                    costs[k] = pick( dir + k ) + m.bits_mvd( bmx + lr_hex2_x( dir + k ), bmy + lr_hex2_y( dir + k ) );
+                    costs[k] = pick( dir + k ) + m.bits_mvd( bmx + hex2_x( dir + k ), bmy + hex2_y( dir + k ) );
                 bcost &= ~7;
                 bcost = min( bcost, (costs[0] << 3) + 1 );
                 bcost = min( bcost, (costs[1] << 3) + 2 );
@@ -609,9 +577,9 @@ __device__ void lr_me_search( const LrCtx<BD> &m, int mvpx, int mvpy, const int 
                 if( !(bcost & 7) )
                     break;
                 dir += (bcost & 7) - 2;
-                dir = lr_mod6m1( dir + 1 );
-                bmx += lr_hex2_x( dir + 1 );
-                bmy += lr_hex2_y( dir + 1 );
+                dir = mod6m1( dir + 1 );
+                bmx += hex2_x( dir + 1 );
+                bmy += hex2_y( dir + 1 );
             }
         }
         bcost >>= 3;
@@ -625,8 +593,8 @@ __device__ void lr_me_search( const LrCtx<BD> &m, int mvpx, int mvpy, const int 
                 bcost = min( bcost, (c8[k - 1] << 4) + k );
         }
 #undef LR_W
-        bmx += lr_square1_x( bcost & 15 );
-        bmy += lr_square1_y( bcost & 15 );
+        bmx += square1_x( bcost & 15 );
+        bmy += square1_y( bcost & 15 );
         bcost >>= 4;
     }
 #undef LR_COST_MV
@@ -1213,29 +1181,6 @@ __global__ __launch_bounds__( 128 ) void lowres_inter_kernel(
     }
 }
 
-// pixel_avg / pixel_avg_weight_wxh (mc.c:49-87) of two packed dwords: the rounding
-// average at weight 32, else (a*w + b*(64-w) + 32) >> 6 in 16-bit lanes (w in [0, 64]:
-// no clipping needed, 1023*64 + 32 < 2^16)
-template <int BD> __device__ __forceinline__ uint32_t lr_wavg( uint32_t a, uint32_t b, int w )
-{
-    if( w == 32 )
-        return avg_round<BD>( a, b );
-    typedef unsigned short us2 __attribute__( ( ext_vector_type( 2 ) ) );
-    const us2 wa = (us2)(unsigned short)w, wb = (us2)(unsigned short)(64 - w);
-    auto f = [&]( uint32_t x, uint32_t y ) {
-        const us2 r = (__builtin_bit_cast( us2, x ) * wa + __builtin_bit_cast( us2, y ) * wb + (us2)32) >> (us2)6;
-        return __builtin_bit_cast( uint32_t, r );
-    };
-    if constexpr( BD == 8 )
-    {
-        const uint32_t lo = f( __builtin_amdgcn_perm( 0u, a, 0x0c020c00u ), __builtin_amdgcn_perm( 0u, b, 0x0c020c00u ) );
-        const uint32_t hi = f( __builtin_amdgcn_perm( 0u, a, 0x0c030c01u ), __builtin_amdgcn_perm( 0u, b, 0x0c030c01u ) );
-        return __builtin_amdgcn_perm( hi, lo, 0x06020400u );
-    }
-    else
-        return f( a, b );
-}
-
 // TRY_BIDIR (slicetype.c:589-612): the weighted average of the two lists' predictions
 // scored with mbcmp; hpel = the subme <= 1 form (hpel planes addressed directly)
 template <int BD>
@@ -1258,7 +1203,7 @@ __device__ __forceinline__ int lr_bidir( const LrCtx<BD> &m0, const LrCtx<BD> &m
     for( int y = 0; y < LR_NR; y++ )
 #pragma unroll
         for( int k = 0; k < NDW; k++ )
-            ra[y][k] = lr_wavg<BD>( ra[y][k], rb[y][k], w );
+            ra[y][k] = bi_packed_noclip<BD>( ra[y][k], rb[y][k], w );
     return lr_cmp_rows<BD>( m0.fe, ra, m0.satd, m0.q );
 }
 

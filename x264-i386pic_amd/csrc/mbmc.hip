@@ -24,7 +24,7 @@
 // list(s), the bipred weight (32: the rounding average; else pixel_avg_weight_wxh with its clip)
 // and, for list-0-only partitions, mc->weight (mc_weight after the average, as mc_luma does).
 // `pred` is only written.
-#include "hipcommon.h"
+#include "mcdev.h"
 #include "x264hip_mc.h"
 
 namespace x264hip {
@@ -54,74 +54,27 @@ template <int BD> struct McParams
     int n;
 };
 
-// the 4x4 tile of get_ref( mvx, mvy ) (mc.c:221-249, unweighted) at q + the mv's offset
-template <int BD>
-__device__ __forceinline__ void ref_tile( const typename PT<BD>::pixel *q0, const typename PT<BD>::pixel *q1,
-                                          const typename PT<BD>::pixel *q2, const typename PT<BD>::pixel *q3,
-                                          intptr_t at, intptr_t rs, int mvx, int mvy,
-                                          uint32_t ( &r )[4][4 / PT<BD>::PPD] )
-{
-    using pixel = typename PT<BD>::pixel;
-    constexpr int LW = 4 / PT<BD>::PPD;
-    const int idx = ((mvy & 3) << 2) + (mvx & 3);
-    const intptr_t off = at + (intptr_t)(mvy >> 2) * rs + (mvx >> 2);
-    constexpr uint32_t k0 = pack_fields( c_ref0, 2 ), k1 = pack_fields( c_ref1, 2 );
-    const int i0 = field( k0, 2, idx ), i1 = field( k1, 2, idx );
-    // (four separate pointers, not an array or a struct: a select over those goes through memory)
-    const pixel *s1 = (i0 == 0 ? q0 : i0 == 1 ? q1 : i0 == 2 ? q2 : q3) + off + ((mvy & 3) == 3) * rs;
-    const pixel *s2 = (i1 == 0 ? q0 : i1 == 1 ? q1 : i1 == 2 ? q2 : q3) + off + ((mvx & 3) == 3);
-    // both planes always, with no branch between the loads: at a full- or half-pel phase the pair
-    // is one plane at one offset (s2 == s1, the second load hits the line the first brought) and
-    // avg( a, a ) = a; a lane-dependent branch here would put the second plane's latency behind
-    // the first's
-    uint32_t r2[4][LW];
-#pragma unroll
-    for( int y = 0; y < 4; y++ )
-    {
-        load_al_pad<LW>( s1 + y * rs, r[y] );
-        load_al_pad<LW>( s2 + y * rs, r2[y] );
-    }
-#pragma unroll
-    for( int y = 0; y < 4; y++ )
-#pragma unroll
-        for( int k = 0; k < LW; k++ )
-            r[y][k] = avg_round<BD>( r[y][k], r2[y][k] );
-}
-
-// mc.avg of two pixels' worth of packed words: weight 32 = pixel_avg_wxh, else
-// pixel_avg_weight_wxh (mc.c:63-87; the clamp-first shift of shr_clip)
-template <int BD> __device__ __forceinline__ uint32_t bi_packed( uint32_t a, uint32_t b, int w1 )
-{
-    if( w1 == 32 )
-        return avg_round<BD>( a, b );
-    constexpr int PPD = PT<BD>::PPD, SH = 32 / PPD;
-    const int w2 = 64 - w1;
-    uint32_t r = 0;
-#pragma unroll
-    for( int k = 0; k < PPD; k++ )
-        r |= (uint32_t)shr_clip<BD, 6>( upix<BD>( a, k ) * w1 + upix<BD>( b, k ) * w2 + 32 ) << (SH * k);
-    return r;
-}
-
 // one plane's 4x4 tile of a partition: MC_LUMA / MC_LUMA_BI (macroblock.c:31-35, 104-110)
 template <int BD, bool GEN>
 __device__ __forceinline__ void mc_plane( const McPlanes<BD> &q0, const McPlanes<BD> &q1, intptr_t at, intptr_t rs,
                                           int lists, int biw, int mvx0, int mvy0, int mvx1, int mvy1,
                                           const RsWeight &wt, uint32_t ( &r )[4][4 / PT<BD>::PPD] )
 {
+    // ref_tile's both-planes form: a lane-dependent branch between the planes would put the
+    // second plane's latency behind the first's in this streaming kernel
     constexpr int LW = 4 / PT<BD>::PPD;
     if constexpr( !GEN )
-        ref_tile<BD>( q0.p0, q0.p1, q0.p2, q0.p3, at, rs, mvx0, mvy0, r );
+        ref_tile<BD, LW, true>( q0.p0, q0.p1, q0.p2, q0.p3, at, rs, mvx0, mvy0, r );
     else
     {
         // the first (or only) list's tile, then list 1's for a bipred partition
         const bool one = lists == 2;
-        ref_tile<BD>( one ? q1.p0 : q0.p0, one ? q1.p1 : q0.p1, one ? q1.p2 : q0.p2, one ? q1.p3 : q0.p3, at, rs,
-                      one ? mvx1 : mvx0, one ? mvy1 : mvy0, r );
+        ref_tile<BD, LW, true>( one ? q1.p0 : q0.p0, one ? q1.p1 : q0.p1, one ? q1.p2 : q0.p2, one ? q1.p3 : q0.p3,
+                                at, rs, one ? mvx1 : mvx0, one ? mvy1 : mvy0, r );
         if( lists == 3 )
         {
             uint32_t s[4][LW];
-            ref_tile<BD>( q1.p0, q1.p1, q1.p2, q1.p3, at, rs, mvx1, mvy1, s );
+            ref_tile<BD, LW, true>( q1.p0, q1.p1, q1.p2, q1.p3, at, rs, mvx1, mvy1, s );
 #pragma unroll
             for( int y = 0; y < 4; y++ )
 #pragma unroll
@@ -160,10 +113,8 @@ __device__ __forceinline__ void chroma_pairs( const typename PT<BD>::pixel *s, i
                                               rs_us2 ( &m )[ROWS][2] )
 {
     constexpr int NDW = BD == 8 ? 2 : 3;    // three (U, V) pairs of a source row
-    const uint32_t dx = mvx & 7, dy = mvyc & 7;
-    const rs_us2 kA = (rs_us2)(uint16_t)((8 - dx) * (8 - dy)), kB = (rs_us2)(uint16_t)(dx * (8 - dy));
-    const rs_us2 kC = (rs_us2)(uint16_t)((8 - dx) * dy), kD = (rs_us2)(uint16_t)(dx * dy);
-    s += (intptr_t)(mvyc >> 3) * rcs + (mvx >> 3) * 2;
+    const ChromaTapsPk t = chroma_taps_pk( mvx, mvyc );
+    s += chroma_off( mvx, mvyc, rcs );
     uint32_t w[ROWS + 1][NDW];
 #pragma unroll
     for( int y = 0; y <= ROWS; y++ )
@@ -184,17 +135,7 @@ __device__ __forceinline__ void chroma_pairs( const typename PT<BD>::pixel *s, i
     for( int y = 0; y < ROWS; y++ )
 #pragma unroll
         for( int x = 0; x < 2; x++ )
-            m[y][x] = (kA * nv_pair<BD>( w[y], x ) + kB * nv_pair<BD>( w[y], x + 1 ) + kC * nv_pair<BD>( w[y + 1], x ) +
-                       kD * nv_pair<BD>( w[y + 1], x + 1 ) + (rs_us2)32) >> (rs_us2)6;
-}
-
-template <int BD> __device__ __forceinline__ int bi_pixel( int a, int b, int w1 )
-{
-    return shr_clip<BD, 6>( a * w1 + b * (64 - w1) + 32 );
-}
-template <int BD> __device__ __forceinline__ int weigh_pixel( int v, const RsWeight &wt )
-{
-    return clip_pix<BD>( ((v * wt.scale + wt.rnd) >> wt.denom) + wt.offset );
+            m[y][x] = chroma_pair<BD>( t, w[y], w[y + 1], x );
 }
 
 template <int BD, int IPIX, int CF, bool GEN>
@@ -271,8 +212,8 @@ __global__ __launch_bounds__( 256 ) void mb_mc_kernel( const McParams<BD> a )
                         if( biw == 32 )
                             m[cy][cx] = (m[cy][cx] + m1[cy][cx] + (rs_us2)1) >> (rs_us2)1;
                         else
-                            m[cy][cx] = (rs_us2){ (uint16_t)bi_pixel<BD>( m[cy][cx].x, m1[cy][cx].x, biw ),
-                                                  (uint16_t)bi_pixel<BD>( m[cy][cx].y, m1[cy][cx].y, biw ) };
+                            m[cy][cx] = (rs_us2){ (uint16_t)bi_weighted_px<BD>( m[cy][cx].x, m1[cy][cx].x, biw ),
+                                                  (uint16_t)bi_weighted_px<BD>( m[cy][cx].y, m1[cy][cx].y, biw ) };
                     }
             }
             else if( lists == 1 && (a.wu.on | a.wv.on) )
@@ -281,14 +222,7 @@ __global__ __launch_bounds__( 256 ) void mb_mc_kernel( const McParams<BD> a )
                 for( int cy = 0; cy < ROWS; cy++ )
 #pragma unroll
                     for( int cx = 0; cx < 2; cx++ )
-                    {
-                        int lo = m[cy][cx].x, hi = m[cy][cx].y;
-                        if( a.wu.on )
-                            lo = weigh_pixel<BD>( lo, a.wu );
-                        if( a.wv.on )
-                            hi = weigh_pixel<BD>( hi, a.wv );
-                        m[cy][cx] = (rs_us2){ (uint16_t)lo, (uint16_t)hi };
-                    }
+                        m[cy][cx] = weigh_pair<BD>( m[cy][cx], a.wu, a.wv );
             }
         }
         uint32_t c[ROWS][LW];

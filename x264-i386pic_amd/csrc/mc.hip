@@ -4,7 +4,7 @@
 //  * SAD / SATD of blocks fetched at quarter-pel positions (get_ref, mc.c:221-249,
 //    with x264_hpel_ref0/1 of common/tables.c:183-184 and pixel_avg mc.c:49-61),
 //    i.e. the candidate costs of refine_subpel (encoder/me.c:865-992).
-#include "hipcommon.h"
+#include "mcdev.h"
 
 #include <stdlib.h>
 #include <type_traits>
@@ -638,43 +638,11 @@ hipError_t launch_hpel_filter( const typename PT<BD>::pixel *src, typename PT<BD
 }
 
 // ------------------------------------------------------------ qpel candidates
-constexpr uint8_t c_hpel_ref0[16] = { 0, 1, 1, 1, 0, 1, 1, 1, 2, 3, 3, 3, 0, 1, 1, 1 };
-constexpr uint8_t c_hpel_ref1[16] = { 0, 0, 1, 0, 2, 2, 3, 2, 2, 2, 3, 2, 2, 2, 3, 2 };
-
-// rounding-up average of packed pixels, (a + b + 1) >> 1 per pixel (pixel_avg, mc.c:57)
-template <int BD> __device__ __forceinline__ uint32_t avg_packed( uint32_t a, uint32_t b )
-{
-    constexpr uint32_t keep = BD == 8 ? 0x7F7F7F7Fu : 0x7FFF7FFFu;
-    return (a | b) - (((a ^ b) >> 1) & keep);
-}
-
-// Row of NDW packed dwords at an arbitrary pixel address from dword-aligned loads:
-// the NDW words of an aligned row, else the NDW + 1 words holding it realigned with
-// v_alignbyte (no byte outside the row's dwords is touched).  On gfx950 the address
-// path takes ~14.6 cycles per CU for a wave's dword-aligned dwordx2 / x3 / x4 load of
-// 8-16 bytes per lane against 28.5 (x2) and 56.8 (x4) when the lanes' addresses are
-// byte-misaligned (tools/ta_probe.hip, profiles/r01d_ta_probe.txt).
-template <int NDW>
-__device__ __forceinline__ void load_row_al( const void *p, uint32_t (&out)[NDW] )
-{
-    typedef const __attribute__( ( address_space( 1 ) ) ) uint32_t gword;
-    const uint32_t sh = (uint32_t)((uintptr_t)p & 3);
-    gword *base = (gword *)((uintptr_t)p & ~(uintptr_t)3);
-    uint32_t w[NDW + 1];
-#pragma unroll
-    for( int i = 0; i < NDW; i++ )
-        w[i] = base[i];
-    w[NDW] = base[sh ? NDW : NDW - 1];      // branch-free: re-reads word NDW-1 when aligned
-#pragma unroll
-    for( int i = 0; i < NDW; i++ )
-        out[i] = __builtin_amdgcn_alignbyte( w[i + 1], w[i], sh );
-}
-
 // One lane per candidate (LD = 0 at 8 bit, 1 at 10 bit).  The second plane pointer equals the first when the
 // qpel phase needs one plane (avg(a, a) = a), so every band's rows are issued
 // as one burst of loads; rows are fetched with unaligned 4/8/16-byte global
 // loads (amdhsa runs with unaligned access enabled: no alignbyte) or, LD = 1,
-// dword-aligned loads + alignbyte (load_row_al); the 8-bit
+// dword-aligned loads + alignbyte (load_al); the 8-bit
 // rounding average is one v_lerp_u8 per dword (pixel_avg, mc.c:57).
 template <int BD, int OP, int IPIX, int LD>
 __device__ __forceinline__ int subpel_score( const typename PT<BD>::pixel *a, intptr_t fs,
@@ -687,13 +655,9 @@ __device__ __forceinline__ int subpel_score( const typename PT<BD>::pixel *a, in
     constexpr int W = pix_w( IPIX ), H = pix_h( IPIX );
     constexpr int NDW = W / PPD;
     constexpr int BAND = (16 / NDW) < 4 ? 4 : (16 / NDW) > H ? H : (16 / NDW);   // rows per load burst
-    const int idx = ((qy & 3) << 2) + (qx & 3);
-    const intptr_t off = (intptr_t)(qy >> 2) * rs + (qx >> 2);
-    constexpr uint32_t k0 = pack_fields( c_hpel_ref0, 2 ), k1 = pack_fields( c_hpel_ref1, 2 );
-    const int i0 = field( k0, 2, idx ), i1 = field( k1, 2, idx );
-    const pixel *s1 = (i0 == 0 ? p0 : i0 == 1 ? p1 : i0 == 2 ? p2 : p3) + off + ((qy & 3) == 3) * rs;
-    const pixel *s2 = (i1 == 0 ? p0 : i1 == 1 ? p1 : i1 == 2 ? p2 : p3) + off + ((qx & 3) == 3);
-    if( !(idx & 5) )
+    const RefPhase ph = ref_phase( qx, qy, rs );
+    const pixel *s1 = ref_ptr0( ph, p0, p1, p2, p3, rs ), *s2 = ref_ptr1( ph, p0, p1, p2, p3 );
+    if( !ph.two() )
         s2 = s1;
     uint32_t acc = 0;
     int sum = 0;
@@ -712,9 +676,9 @@ __device__ __forceinline__ int subpel_score( const typename PT<BD>::pixel *a, in
             }
             else
             {
-                load_row_al<NDW>( a + (ty + y) * fs, fr[y] );
-                load_row_al<NDW>( s1 + (ty + y) * rs, rr[y] );
-                load_row_al<NDW>( s2 + (ty + y) * rs, r2[y] );
+                load_al<NDW>( a + (ty + y) * fs, fr[y] );
+                load_al<NDW>( s1 + (ty + y) * rs, rr[y] );
+                load_al<NDW>( s2 + (ty + y) * rs, r2[y] );
             }
         }
 #pragma unroll
@@ -876,15 +840,15 @@ __global__ __launch_bounds__( 256 ) void subpel_qpel9_kernel( const typename PT<
 #pragma unroll
             for( int y = 0; y < 4; y++ )
             {
-                load_row_al<N8>( a + (ty + y) * fs + tx, f[y] );
-                load_row_al<N8>( gcc + (ty + y) * rs + tx, cc[y] );
-                load_row_al<N8 + 1>( gxc + (ty + y) * rs + tx, xc[y] );
+                load_al<N8>( a + (ty + y) * fs + tx, f[y] );
+                load_al<N8>( gcc + (ty + y) * rs + tx, cc[y] );
+                load_al<N8 + 1>( gxc + (ty + y) * rs + tx, xc[y] );
             }
 #pragma unroll
             for( int y = 0; y < 5; y++ )
             {
-                load_row_al<N8>( gcy + (ty + y) * rs + tx, cy[y] );
-                load_row_al<N8 + 1>( gxy + (ty + y) * rs + tx, xy[y] );
+                load_al<N8>( gcy + (ty + y) * rs + tx, cy[y] );
+                load_al<N8 + 1>( gxy + (ty + y) * rs + tx, xy[y] );
             }
             // SATD: the fenc tile's biased Hadamards once for the nine candidates (had8x4_biased)
             uint32_t hf[16];

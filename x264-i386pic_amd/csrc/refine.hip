@@ -32,7 +32,7 @@
 // mc_chroma (mc.c:252-283) for its block from the interleaved plane, weighting it and scoring
 // it with the 4x4 Hadamard (or SAD); 4:4:4 (EXT 2): the luma tile schedule over the U and V
 // hpel planes with get_ref and weight[1] / weight[2].
-#include "hipcommon.h"
+#include "mcdev.h"
 
 namespace x264hip {
 
@@ -56,41 +56,18 @@ __device__ __forceinline__ uint32_t tile_cost( const uint32_t (&fa)[4][8 / PT<BD
                                                intptr_t rs, int mvx, int mvy, const RsWeight wt = {},
                                                lds_cu32 *fl = nullptr )
 {
-    using pixel = typename PT<BD>::pixel;
     constexpr int HDW = 8 / PT<BD>::PPD, LW = HDW * TW / 8;   // words of a row; of the tile's row
-    const int idx = ((mvy & 3) << 2) + (mvx & 3);
-    const intptr_t off = (intptr_t)(mvy >> 2) * rs + (mvx >> 2);
-    constexpr uint32_t k0 = pack_fields( c_ref0, 2 ), k1 = pack_fields( c_ref1, 2 );
-    const int i0 = field( k0, 2, idx ), i1 = field( k1, 2, idx );
-    // (four separate pointers, not an array: a select over an array's elements was folded into
-    // an indexed load, which put the array in scratch memory)
-    const pixel *s1 = (i0 == 0 ? q0 : i0 == 1 ? q1 : i0 == 2 ? q2 : q3) + off + ((mvy & 3) == 3) * rs;
-    const pixel *s2 = (i1 == 0 ? q0 : i1 == 1 ? q1 : i1 == 2 ? q2 : q3) + off + ((mvx & 3) == 3);
     // rows as dword-aligned loads realigned with v_alignbyte: the address path takes a
     // byte-misaligned 8-byte lane load at ~2x the cost of an aligned 12-byte one
-    // (profiles/r01d_ta_probe.txt), and it binds this kernel (TA busy ~100 %, r04d)
-    uint32_t r1[4][HDW];
+    // (profiles/r01d_ta_probe.txt), and it binds this kernel (TA busy ~100 %, r04d); the
+    // branchy form: the second plane is loaded only at a two-plane phase
+    uint32_t t[4][LW], r1[4][HDW];
+    ref_tile<BD, LW, false>( q0, q1, q2, q3, 0, rs, mvx, mvy, t );
 #pragma unroll
     for( int y = 0; y < 4; y++ )
-    {
-        uint32_t t[LW];
-        load_al_pad<LW>( s1 + y * rs, t );
 #pragma unroll
         for( int k = 0; k < HDW; k++ )
-            r1[y][k] = k < LW ? t[k] : 0u;
-    }
-    if( idx & 5 )                           // two planes: the rounding average (one plane: avg( a, a ) = a)
-    {
-        uint32_t r2[4][LW];
-#pragma unroll
-        for( int y = 0; y < 4; y++ )
-            load_al_pad<LW>( s2 + y * rs, r2[y] );
-#pragma unroll
-        for( int y = 0; y < 4; y++ )
-#pragma unroll
-            for( int k = 0; k < LW; k++ )
-                r1[y][k] = avg_round<BD>( r1[y][k], r2[y][k] );
-    }
+            r1[y][k] = k < LW ? t[y][k] : 0u;
     if constexpr( WGT )
         if( wt.on )
 #pragma unroll
@@ -204,10 +181,8 @@ __device__ __forceinline__ uint32_t nv_pair_cost( const typename PT<BD>::pixel *
                                                   const RsWeight &wv, bool satd, bool hh )
 {
     constexpr int NDW = BD == 8 ? 3 : 5;    // five (U, V) pairs of a source row
-    const uint32_t dx = mvx & 7, dy = mvyc & 7;
-    const rs_us2 kA = (rs_us2)(uint16_t)((8 - dx) * (8 - dy)), kB = (rs_us2)(uint16_t)(dx * (8 - dy));
-    const rs_us2 kC = (rs_us2)(uint16_t)((8 - dx) * dy), kD = (rs_us2)(uint16_t)(dx * dy);
-    s += (intptr_t)(mvyc >> 3) * rcs + (mvx >> 3) * 2;
+    const ChromaTapsPk tp = chroma_taps_pk( mvx, mvyc );
+    s += chroma_off( mvx, mvyc, rcs );
     uint32_t w[3][NDW];
 #pragma unroll
     for( int r = 0; r < 3; r++ )
@@ -218,17 +193,9 @@ __device__ __forceinline__ uint32_t nv_pair_cost( const typename PT<BD>::pixel *
 #pragma unroll
         for( int x = 0; x < 4; x++ )
         {
-            rs_us2 m = (kA * nv_pair<BD>( w[y], x ) + kB * nv_pair<BD>( w[y], x + 1 ) + kC * nv_pair<BD>( w[y + 1], x ) +
-                        kD * nv_pair<BD>( w[y + 1], x + 1 ) + (rs_us2)32) >> (rs_us2)6;
+            rs_us2 m = chroma_pair<BD>( tp, w[y], w[y + 1], x );
             if( wu.on | wv.on )
-            {
-                int lo = m.x, hi = m.y;
-                if( wu.on )
-                    lo = clip_pix<BD>( ((lo * wu.scale + wu.rnd) >> wu.denom) + wu.offset );
-                if( wv.on )
-                    hi = clip_pix<BD>( ((hi * wv.scale + wv.rnd) >> wv.denom) + wv.offset );
-                m = (rs_us2){ (uint16_t)lo, (uint16_t)hi };
-            }
+                m = weigh_pair<BD>( m, wu, wv );
             d[y][x] = __builtin_bit_cast( x264hip_short2, fb[y][x] ) - as_s2( m );
         }
     x264hip_short2 acc = { 0, 0 };
@@ -892,10 +859,7 @@ namespace {
 constexpr int SR_MVC = 14;                                // candidates per partition (mvc_temp+2 of me.c:195)
 __device__ __forceinline__ uint32_t sr_pack( int a, int b ) { return (uint32_t)(uint16_t)a | ((uint32_t)(uint16_t)b << 16); }
 __device__ __forceinline__ int sr_clip( int v, int lo, int hi ) { return min( max( v, lo ), hi ); }
-// hex2 (me.c:55), square1 (:56) and hex4 (:534-539) as bit fields (offset + bias)
-constexpr uint8_t k_hex2x[8] = { 1, 0, 1, 3, 4, 3, 1, 0 }, k_hex2y[8] = { 0, 2, 4, 4, 2, 0, 0, 2 };   // +2
-constexpr uint8_t k_sq1x[9] = { 1, 1, 1, 0, 2, 0, 0, 2, 2 }, k_sq1y[9] = { 1, 0, 2, 1, 1, 0, 2, 0, 2 };  // +1
-constexpr uint8_t k_mod6m1[8] = { 5, 0, 1, 2, 3, 4, 5, 0 };
+// hex4 (me.c:534-539) as bit fields (offset + bias); hex2, mod6m1 and square1 are hipcommon.h's
 constexpr uint8_t k_hex4x0[8] = { 4, 4, 2, 6, 0, 8, 0, 8 }, k_hex4x1[8] = { 0, 8, 0, 8, 0, 8, 2, 6 };   // +4
 constexpr uint8_t k_hex4y0[8] = { 0, 8, 1, 1, 2, 2, 3, 3 }, k_hex4y1[8] = { 4, 4, 5, 5, 6, 6, 7, 7 };   // +4
 constexpr uint8_t k_psize_shift[7] = { 0, 1, 1, 2, 3, 3, 4 };
@@ -1411,7 +1375,6 @@ __global__ __launch_bounds__( 256 ) void me_search_ref_kernel(
     if( hex )
     {
         // hexagon (me.c:344-403): COST_MV_X3_DIR( -2,0, -1,2, 1,2 ), COST_MV_X3_DIR( 2,0, 1,-2, -1,-2 )
-        constexpr uint32_t h2x = pack_fields( k_hex2x, 3 ), h2y = pack_fields( k_hex2y, 3 );
         evalc( bmx + (g == 0 ? -2 : g == 1 ? -1 : g == 2 ? 1 : 2), bmy + (g == 0 || g == 3 ? 0 : 2), 0, true, c );
         int c2[4];
         evalc( bmx + (g == 0 ? 1 : -1), bmy - 2, 0, g < 2, c2 );
@@ -1426,13 +1389,13 @@ __global__ __launch_bounds__( 256 ) void me_search_ref_kernel(
         if( bcost & 7 )
         {
             int dir = (bcost & 7) - 2;
-            bmx += field( h2x, 3, dir + 1 ) - 2;
-            bmy += field( h2y, 3, dir + 1 ) - 2;
+            bmx += hex2_x( dir + 1 );
+            bmy += hex2_y( dir + 1 );
             for( int i = (i_me_range >> 1) - 1; i > 0 && in_range( bmx, bmy ); i-- )
             {
                 // COST_MV_X3_DIR( hex2[dir], hex2[dir+1], hex2[dir+2] )
                 const int d = dir + (g < 3 ? g : 0);
-                evalc( bmx + field( h2x, 3, d ) - 2, bmy + field( h2y, 3, d ) - 2, 0, g < 3, c );
+                evalc( bmx + hex2_x( d ), bmy + hex2_y( d ), 0, g < 3, c );
                 nf += 3;
                 bcost &= ~7;
                 if( (c[0] << 3) + 1 < bcost ) bcost = (c[0] << 3) + 1;
@@ -1441,9 +1404,9 @@ __global__ __launch_bounds__( 256 ) void me_search_ref_kernel(
                 if( !(bcost & 7) )
                     break;
                 dir += (bcost & 7) - 2;
-                dir = field( pack_fields( k_mod6m1, 3 ), 3, dir + 1 );
-                bmx += field( h2x, 3, dir + 1 ) - 2;
-                bmy += field( h2y, 3, dir + 1 ) - 2;
+                dir = mod6m1( dir + 1 );
+                bmx += hex2_x( dir + 1 );
+                bmy += hex2_y( dir + 1 );
             }
         }
         bcost >>= 3;
@@ -1460,9 +1423,8 @@ __global__ __launch_bounds__( 256 ) void me_search_ref_kernel(
         if( (c[2] << 4) + 7 < bcost ) bcost = (c[2] << 4) + 7;
         if( (c[3] << 4) + 8 < bcost ) bcost = (c[3] << 4) + 8;
         nf += 8;
-        constexpr uint32_t s1x = pack_fields( k_sq1x, 2 ), s1y = pack_fields( k_sq1y, 2 );
-        bmx += field( s1x, 2, bcost & 15 ) - 1;
-        bmy += field( s1y, 2, bcost & 15 ) - 1;
+        bmx += square1_x( bcost & 15 );
+        bmy += square1_y( bcost & 15 );
         bcost >>= 4;
     }
 
@@ -1640,37 +1602,6 @@ __constant__ uint8_t c_dia4d[33] = {               // me.c:1064-1075, (d + 1) in
     0x99, 0x11, 0x66, 0x44, 0x85, 0x25, 0x61, 0x49, 0x58, 0x52, 0x16, 0x94, 0x91, 0x19, 0x64, 0x46 };
 __device__ __forceinline__ int dia4d( int j, int c ) { return (int)((c_dia4d[j] >> (2 * c)) & 3) - 1; }
 
-// the lane's 8x4 tile of get_ref( mvx, mvy ) (unweighted)
-template <int BD>
-__device__ __forceinline__ void ref_tile( const typename PT<BD>::pixel *q0, const typename PT<BD>::pixel *q1,
-                                          const typename PT<BD>::pixel *q2, const typename PT<BD>::pixel *q3,
-                                          intptr_t rs, int mvx, int mvy, uint32_t (&r1)[4][8 / PT<BD>::PPD] )
-{
-    using pixel = typename PT<BD>::pixel;
-    constexpr int HDW = 8 / PT<BD>::PPD;
-    const int idx = ((mvy & 3) << 2) + (mvx & 3);
-    const intptr_t off = (intptr_t)(mvy >> 2) * rs + (mvx >> 2);
-    constexpr uint32_t k0 = pack_fields( c_ref0, 2 ), k1 = pack_fields( c_ref1, 2 );
-    const int i0 = field( k0, 2, idx ), i1 = field( k1, 2, idx );
-    const pixel *s1 = (i0 == 0 ? q0 : i0 == 1 ? q1 : i0 == 2 ? q2 : q3) + off + ((mvy & 3) == 3) * rs;
-    const pixel *s2 = (i1 == 0 ? q0 : i1 == 1 ? q1 : i1 == 2 ? q2 : q3) + off + ((mvx & 3) == 3);
-#pragma unroll
-    for( int y = 0; y < 4; y++ )
-        load_al_pad<HDW>( s1 + y * rs, r1[y] );
-    if( idx & 5 )
-    {
-        uint32_t r2[4][HDW];
-#pragma unroll
-        for( int y = 0; y < 4; y++ )
-            load_al_pad<HDW>( s2 + y * rs, r2[y] );
-#pragma unroll
-        for( int y = 0; y < 4; y++ )
-#pragma unroll
-            for( int k = 0; k < HDW; k++ )
-                r1[y][k] = avg_round<BD>( r1[y][k], r2[y][k] );
-    }
-}
-
 template <int BD, int IPIX, bool SATD>
 __global__ __launch_bounds__( 256 ) void me_refine_bidir_kernel(
     const typename PT<BD>::pixel *__restrict__ fenc, intptr_t fs, intptr_t ffs, const typename PT<BD>::pixel *a0,
@@ -1736,8 +1667,12 @@ __global__ __launch_bounds__( 256 ) void me_refine_bidir_kernel(
             if( ok )
             {
                 uint32_t t0[4][HDW], t1[4][HDW];
-                ref_tile<BD>( p0, p1, p2, p3, rs, m0x, m0y, t0 );
-                ref_tile<BD>( r0, r1, r2, r3, rs, m1x, m1y, t1 );
+                // (the branchy get_ref: the second plane only at a two-plane phase)
+                ref_tile<BD, HDW, false>( p0, p1, p2, p3, 0, rs, m0x, m0y, t0 );
+                ref_tile<BD, HDW, false>( r0, r1, r2, r3, 0, rs, m1x, m1y, t1 );
+                // mc.avg with the weight decided once per tile.  The weighted form stays local:
+                // through mcdev.h's bi_weighted the 8-bit byte merge came out 6 instructions
+                // longer (v_and_or_b32 -> v_and_b32 + v_or3_b32) and bidir8 0.7 % slower
                 if( w1 == 32 )
                 {
 #pragma unroll

@@ -9,7 +9,7 @@
 // registers per candidate), one D2H copy brings the costs back, and the host replays the
 // reference's loop over them, early break and all.  Luma is one launch; chroma (outside
 // the lookahead, after a luma weight) one more.
-#include "hipcommon.h"
+#include "mcdev.h"
 #include "x264hip.h"
 
 #include <math.h>
@@ -28,9 +28,6 @@ struct WpCands
     int n;
 };
 
-constexpr uint8_t c_hpel_ref0[16] = { 0, 1, 1, 1, 0, 1, 1, 1, 2, 3, 3, 3, 0, 1, 1, 1 };   // common/tables.c:183
-constexpr uint8_t c_hpel_ref1[16] = { 0, 0, 1, 0, 2, 2, 3, 2, 2, 2, 3, 2, 2, 2, 3, 2 };   // common/tables.c:184
-
 template <int BD>
 __device__ __forceinline__ void wp_row8( const typename PT<BD>::pixel *p, int (&o)[8] )
 {
@@ -40,13 +37,6 @@ __device__ __forceinline__ void wp_row8( const typename PT<BD>::pixel *p, int (&
 #pragma unroll
     for( int k = 0; k < 8; k++ )
         o[k] = upix<BD>( w[k / PPD], k % PPD );
-}
-
-// mc_weight's per-pixel op (common/mc.c:117-137): rnd = 1 << (denom-1) or 0 for denom 0
-template <int BD>
-__device__ __forceinline__ int wp_px( int v, int scale, int denom, int rnd, int off )
-{
-    return clip_pix<BD>( ((v * scale + rnd) >> denom) + off );
 }
 
 __device__ __forceinline__ int dpp_i( int v, int ctrl )
@@ -102,17 +92,15 @@ __global__ __launch_bounds__( 256 ) void wp_cost8_kernel( const typename PT<BD>:
     else if constexpr( MV == 1 )
     {
         const int mvx = mvs[2 * b] + 32 * bx, mvy = mvs[2 * b + 1] + 32 * by;
-        const int q = ((mvy & 3) << 2) + (mvx & 3);
-        const intptr_t off = (intptr_t)(mvy >> 2) * rs + (mvx >> 2) + (intptr_t)r * rs;
-        const typename PT<BD>::pixel *P[4] = { r0, r1, r2, r3 };
-        const typename PT<BD>::pixel *s1 = P[field( pack_fields( c_hpel_ref0, 2 ), 2, q )] + off + ((mvy & 3) == 3) * rs;
+        // get_ref of the lane's row (the second plane only at a two-plane phase)
+        const RefPhase ph = ref_phase( mvx, mvy, rs, (intptr_t)r * rs );
         constexpr int PPD = PT<BD>::PPD, NDW = 8 / PPD;
         uint32_t w1[NDW];
-        load_al_pad<NDW>( s1, w1 );
-        if( q & 5 )
+        load_al_pad<NDW>( ref_ptr0( ph, r0, r1, r2, r3, rs ), w1 );
+        if( ph.two() )
         {
             uint32_t w2[NDW];
-            load_al_pad<NDW>( P[field( pack_fields( c_hpel_ref1, 2 ), 2, q )] + off + ((mvx & 3) == 3), w2 );
+            load_al_pad<NDW>( ref_ptr1( ph, r0, r1, r2, r3 ), w2 );
 #pragma unroll
             for( int i = 0; i < NDW; i++ )
                 w1[i] = avg_round<BD>( w1[i], w2[i] );
@@ -138,7 +126,7 @@ __global__ __launch_bounds__( 256 ) void wp_cost8_kernel( const typename PT<BD>:
         int d[8];
 #pragma unroll
         for( int i = 0; i < 8; i++ )
-            d[i] = (wtd ? wp_px<BD>( g[i], scale, denom, rnd, off ) : g[i]) - f[i];
+            d[i] = (wtd ? weigh_pixel<BD>( g[i], scale, rnd, denom, off ) : g[i]) - f[i];
         uint32_t t = 0;
         if constexpr( SATD )
         {
@@ -223,8 +211,8 @@ __global__ __launch_bounds__( 256 ) void wp_chroma_kernel( const typename PT<BD>
     if constexpr( MV )
     {
         const int mvx = mvs[2 * b], mvy = (2 * mvs[2 * b + 1]) >> (H == 8 ? 1 : 0);
-        const int dx = mvx & 7, dy = mvy & 7;
-        const int cA = (8 - dx) * (8 - dy), cB = dx * (8 - dy), cC = (8 - dx) * dy, cD = dx * dy;
+        const ChromaTaps t = chroma_taps( mvx, mvy );
+        const int cA = t.cA, cB = t.cB, cC = t.cC, cD = t.cD;
         const typename PT<BD>::pixel *s =
             ref + (intptr_t)(H * by + r + (mvy >> 3)) * rs + 16 * bx + (mvx >> 3) * 2 + pl;
         constexpr int NDW = (18 + PPD - 1) / PPD;
@@ -261,7 +249,7 @@ __global__ __launch_bounds__( 256 ) void wp_chroma_kernel( const typename PT<BD>
         int s = -sf;
 #pragma unroll
         for( int i = 0; i < 8; i++ )
-            s += wtd ? wp_px<BD>( g[i], scale, denom, rnd, off ) : g[i];
+            s += wtd ? weigh_pixel<BD>( g[i], scale, rnd, denom, off ) : g[i];
         s += dpp_i( s, 0xB1 );
         s += dpp_i( s, 0x4E );
         s += dpp_i( s, 0x141 );
