@@ -33,6 +33,7 @@ __all__ = [
     "mbtree_propagate", "mbtree_finish", "mbtree_plan", "mbtree_step", "MbtreeStep",
     "mb_mc", "Mc",
     "deblock_strength", "deblock_frames", "chroma_qp_table", "Deblock", "DeblockStrength",
+    "mb_encode_inter", "MbEnc", "MBENC_INTRA", "MBENC_T8x8", "MBENC_D16x16", "MBENC_SKIP", "MBENC_OUTPUTS",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -337,8 +338,8 @@ def cqm_dequant(scaling_lists, transform_8x8=True):
 
 
 # ----------------------------------------------------------------- declarations
-# Every function of include/x264hip.h, include/x264hip_mbtree.h, include/x264hip_mc.h and
-# include/x264hip_deblock.h, once:
+# Every function of include/x264hip.h, include/x264hip_mbtree.h, include/x264hip_mc.h,
+# include/x264hip_deblock.h and include/x264hip_mbenc.h, once:
 # "return:parameters", one letter each, in the struct module's spelling where it has one.
 # tests/test_abi.py checks the first two tables against x264hip.h's prototypes,
 # tests/test_cpu_mbtree.py the third against x264hip_mbtree.h's, tests/test_cpu_mc.py the fourth
@@ -460,6 +461,11 @@ _DEBLOCK = {
 _DEBLOCK_PLAIN = {
     "deblock_strength": "i:PiiiPP",
 }
+# include/x264hip_mbenc.h: x264hip_8_<name> and x264hip_10_<name> (tests/test_cpu_mbenc.py checks
+# them against the header's prototypes)
+_MBENC = {
+    "mb_encode_inter": "i:PiiiP",
+}
 
 
 def _declare(L):
@@ -482,6 +488,9 @@ def _declare(L):
             declare(getattr(L, f"x264hip_{bd}_{name}"), sig)
     for name, sig in _DEBLOCK_PLAIN.items():
         declare(getattr(L, f"x264hip_{name}"), sig)
+    for name, sig in _MBENC.items():
+        for bd in (8, 10):
+            declare(getattr(L, f"x264hip_{bd}_{name}"), sig)
 
 
 # ----------------------------------------------------------------- CQM
@@ -1350,6 +1359,97 @@ def deblock_frames(luma, origin, stride, mb_width, mb_height, qp, mb_flags, bs, 
     name = f"x264hip_{bd}_deblock_frames"
     _rc(getattr(lib(), name)(_c.byref(d), mb_width, mb_height, n, _stream()), name)
     return luma, planes
+
+
+# ----------------------------------------------------------------- inter MB encode (include/x264hip_mbenc.h)
+MBENC_INTRA, MBENC_T8x8, MBENC_D16x16, MBENC_SKIP = 1, 2, 4, 8
+
+
+class MbEnc(_c.Structure):
+    """x264hip_mbenc_t"""
+    _fields_ = [("chroma_format", _c.c_int32), ("b_dct_decimate", _c.c_int32), ("chroma_qp_table", _P),
+                ("quant4_mf", _P), ("quant4_bias", _P), ("quant8_mf", _P), ("quant8_bias", _P),
+                ("dequant4_mf", _P), ("dequant8_mf", _P),
+                ("fenc", _P), ("fenc_stride", _IP), ("fenc_frame_stride", _IP),
+                ("fenc_chroma", _P), ("fenc_chroma_stride", _IP), ("fenc_chroma_frame_stride", _IP),
+                ("pred", _P), ("pred_stride", _IP), ("pred_frame_stride", _IP),
+                ("pred_chroma", _P), ("pred_chroma_stride", _IP), ("pred_chroma_frame_stride", _IP),
+                ("recon", _P), ("recon_stride", _IP), ("recon_frame_stride", _IP),
+                ("recon_chroma", _P), ("recon_chroma_stride", _IP), ("recon_chroma_frame_stride", _IP),
+                ("qp", _P), ("mb_flags", _P), ("level", _P), ("chroma_dc", _P), ("nnz", _P), ("cbp", _P),
+                ("nz", _P), ("flags_out", _P)]
+
+
+MBENC_OUTPUTS = ("level", "chroma_dc", "nnz", "cbp", "nz", "flags_out")
+
+
+def mb_encode_inter(fenc, pred, mb_width, mb_height, nframes, qp, mb_flags, quant4, dequant4_mf, quant8=None,
+                    dequant8_mf=None, chroma_format=0, fenc_chroma=None, pred_chroma=None, recon=None,
+                    recon_chroma=None, b_dct_decimate=True, qp_table=None, chroma_qp_index_offset=0, outs=None):
+    """x264_macroblock_encode of every inter macroblock of nframes frames (x264hip_*_mb_encode_inter,
+    include/x264hip_mbenc.h).  A plane is (tensor, origin, stride, frame_stride): pixel (0,0) of
+    frame 0 at element `origin`, strides in elements; chroma planes are interleaved NV12 / NV16.
+    pred / pred_chroma are what mb_mc wrote; recon / recon_chroma None reconstruct in place.
+    qp int8 [mbs], mb_flags uint8 [mbs] (MBENC_*); quant4 = (quant4_mf, quant4_bias) and quant8
+    the device copies of cqm_init's tables, dequant4_mf / dequant8_mf of cqm_dequant's (quant8 and
+    dequant8_mf None: no transform-8 macroblocks).  qp_table: h->chroma_qp_table (host uint8 array),
+    default chroma_qp_table(depth, chroma_qp_index_offset).  outs: {name: tensor} for any of
+    MBENC_OUTPUTS to write into (intra macroblocks' elements stay as they are); the others are
+    allocated zeroed.  Returns a dict: recon, recon_chroma (the plane tuples) and MBENC_OUTPUTS."""
+    import torch
+    bd = _pix_bd(pred[0])
+    cf = int(chroma_format)
+    if cf not in (0, 1, 2):
+        raise ValueError("mb_encode_inter: chroma_format is 0 (luma only), 1 (4:2:0) or 2 (4:2:2)")
+    if cf and (fenc_chroma is None or pred_chroma is None):
+        raise ValueError("mb_encode_inter: the chroma format needs fenc_chroma and pred_chroma")
+    if (quant8 is None) != (dequant8_mf is None):
+        raise ValueError("mb_encode_inter: quant8 and dequant8_mf come together")
+    if mb_width < 0 or mb_height < 0 or nframes < 0:
+        raise ValueError("mb_encode_inter: negative size")
+    table = chroma_qp_table(bd, chroma_qp_index_offset) if qp_table is None else \
+        np.ascontiguousarray(np.asarray(qp_table, np.uint8))
+    if table.size < 52 + 6 * (bd - 8):
+        raise ValueError("mb_encode_inter: the chroma qp table needs QP_MAX_SPEC + 1 entries")
+    nmb = nframes * mb_width * mb_height
+    if qp.numel() < nmb or mb_flags.numel() < nmb:
+        raise ValueError("mb_encode_inter: qp and mb_flags need one element per macroblock")
+    recon = pred if recon is None else recon
+    recon_chroma = pred_chroma if recon_chroma is None else recon_chroma
+    cdt = torch.int16 if bd == 8 else torch.int32
+    shapes = {"level": ((nmb, 48, 16), cdt), "chroma_dc": ((nmb, 2, 8), cdt), "nnz": ((nmb, 48), torch.uint8),
+              "cbp": ((nmb,), torch.int32), "nz": ((nmb,), torch.int32), "flags_out": ((nmb,), torch.uint8)}
+    out = dict(outs or {})
+    for name, (shape, dt) in shapes.items():
+        if name not in out:
+            out[name] = torch.zeros(shape, dtype=dt, device=pred[0].device)
+        elif out[name].dtype != dt or out[name].numel() < int(np.prod(shape)) or not out[name].is_contiguous():
+            raise ValueError(f"mb_encode_inter: {name} must be a contiguous {dt} tensor of {shape}")
+    e = MbEnc()
+    e.chroma_format, e.b_dct_decimate = cf, int(bool(b_dct_decimate))
+    e.chroma_qp_table = table.ctypes.data
+    e.quant4_mf, e.quant4_bias, e.dequant4_mf = _ptr(quant4[0]).value, _ptr(quant4[1]).value, _ptr(dequant4_mf).value
+    if quant8 is not None:
+        e.quant8_mf, e.quant8_bias, e.dequant8_mf = _ptr(quant8[0]).value, _ptr(quant8[1]).value, _ptr(dequant8_mf).value
+    planes = [("fenc", fenc), ("pred", pred), ("recon", recon)]
+    if cf:
+        planes += [("fenc_chroma", fenc_chroma), ("pred_chroma", pred_chroma), ("recon_chroma", recon_chroma)]
+    for name, (t, origin, stride, fstride) in planes:
+        if _pix_bd(t) != bd:
+            raise TypeError("mb_encode_inter: the planes disagree on the bit depth")
+        setattr(e, name, _ptr(t, origin).value)
+        setattr(e, name + "_stride", stride)
+        setattr(e, name + "_frame_stride", fstride)
+    # (torch gives an empty tensor a NULL pointer; with no macroblock the arrays are not read)
+    dummy = _c.addressof(e)
+    e.qp = _ptr(qp).value or dummy
+    e.mb_flags = _ptr(mb_flags).value or dummy
+    for name in MBENC_OUTPUTS:
+        setattr(e, name, _ptr(out[name]).value or dummy)
+    fname = f"x264hip_{bd}_mb_encode_inter"
+    _rc(getattr(lib(), fname)(_c.byref(e), mb_width, mb_height, nframes, _stream()), fname)
+    out["recon"], out["recon_chroma"] = recon, recon_chroma if cf else None
+    return out
 
 
 def plane_stride(width, pad=PAD):

@@ -9,134 +9,12 @@
 //   QUANT_ONE      reference common/quant.c:50-57 (uint32 arithmetic), entries :59-104
 // Every block lives in one lane's registers; pixels arrive as aligned dwords
 // realigned with v_alignbyte_b32, coefficients leave as contiguous stores.
-#include "hipcommon.h"
+#include "txdev.h"
 #include <stdlib.h>
 
 namespace x264hip {
 
 // ---------------------------------------------------------------- helpers
-template <int BD, int N>
-__device__ __forceinline__ void load_diff( int (&d)[N][N], const typename PT<BD>::pixel *a, intptr_t sa,
-                                           const typename PT<BD>::pixel *b, intptr_t sb )
-{
-    constexpr int NDW = N / PT<BD>::PPD;
-#pragma unroll
-    for( int y = 0; y < N; y++ )
-    {
-        uint32_t ra[NDW], rb[NDW];
-        load_packed<NDW>( a + y * sa, ra );
-        load_packed<NDW>( b + y * sb, rb );
-#pragma unroll
-        for( int x = 0; x < N; x++ )
-            d[y][x] = upix<BD>( ra[x / PT<BD>::PPD], x % PT<BD>::PPD ) - upix<BD>( rb[x / PT<BD>::PPD], x % PT<BD>::PPD );
-    }
-}
-
-
-// sub4x4_dct on a difference block: out[i*4+k] (reference order)
-template <int BD>
-__device__ __forceinline__ void dct4x4_core( int (&d)[4][4], int (&out)[16] )
-{
-    int tmp[4][4];   // tmp[k][i]: second index = source row
-#pragma unroll
-    for( int i = 0; i < 4; i++ )
-    {
-        int s03 = d[i][0] + d[i][3], s12 = d[i][1] + d[i][2];
-        int d03 = d[i][0] - d[i][3], d12 = d[i][1] - d[i][2];
-        tmp[0][i] = sto<BD>( s03 + s12 );
-        tmp[1][i] = sto<BD>( 2 * d03 + d12 );
-        tmp[2][i] = sto<BD>( s03 - s12 );
-        tmp[3][i] = sto<BD>( d03 - 2 * d12 );
-    }
-#pragma unroll
-    for( int i = 0; i < 4; i++ )
-    {
-        int s03 = tmp[i][0] + tmp[i][3], s12 = tmp[i][1] + tmp[i][2];
-        int d03 = tmp[i][0] - tmp[i][3], d12 = tmp[i][1] - tmp[i][2];
-        out[i * 4 + 0] = sto<BD>( s03 + s12 );
-        out[i * 4 + 1] = sto<BD>( 2 * d03 + d12 );
-        out[i * 4 + 2] = sto<BD>( s03 - s12 );
-        out[i * 4 + 3] = sto<BD>( d03 - 2 * d12 );
-    }
-}
-
-// DCT8_1D, reference common/dct.c:332-356 (src/dst via lambdas on indices)
-#define DCT8_1D_ARR( S, D )                                                             \
-    {                                                                                   \
-        int s07 = S( 0 ) + S( 7 ), s16 = S( 1 ) + S( 6 ), s25 = S( 2 ) + S( 5 ),        \
-            s34 = S( 3 ) + S( 4 );                                                      \
-        int a0 = s07 + s34, a1 = s16 + s25, a2 = s07 - s34, a3 = s16 - s25;             \
-        int d07 = S( 0 ) - S( 7 ), d16 = S( 1 ) - S( 6 ), d25 = S( 2 ) - S( 5 ),        \
-            d34 = S( 3 ) - S( 4 );                                                      \
-        int a4 = d16 + d25 + ( d07 + ( d07 >> 1 ) );                                    \
-        int a5 = d07 - d34 - ( d25 + ( d25 >> 1 ) );                                    \
-        int a6 = d07 + d34 - ( d16 + ( d16 >> 1 ) );                                    \
-        int a7 = d16 - d25 + ( d34 + ( d34 >> 1 ) );                                    \
-        D( 0, a0 + a1 );                                                                \
-        D( 1, a4 + ( a7 >> 2 ) );                                                       \
-        D( 2, a2 + ( a3 >> 1 ) );                                                       \
-        D( 3, a5 + ( a6 >> 2 ) );                                                       \
-        D( 4, a0 - a1 );                                                                \
-        D( 5, a6 - ( a5 >> 2 ) );                                                       \
-        D( 6, ( a2 >> 1 ) - a3 );                                                       \
-        D( 7, ( a4 >> 2 ) - a7 );                                                       \
-    }
-
-// sub8x8_dct8 on a difference block (d[y][x]); out[x*8+i] reference order
-template <int BD>
-__device__ __forceinline__ void dct8x8_core( int (&d)[8][8], int (&out)[64] )
-{
-    // column pass in place: column i, SRC(x) = d[x][i]
-#pragma unroll
-    for( int i = 0; i < 8; i++ )
-    {
-#define S( x ) d[x][i]
-#define D( x, v ) t[x] = sto<BD>( v )
-        int t[8];
-        DCT8_1D_ARR( S, D )
-#pragma unroll
-        for( int x = 0; x < 8; x++ )
-            d[x][i] = t[x];
-#undef S
-#undef D
-    }
-    // row pass: row i, SRC(x) = d[i][x], DST(x) = dct[x*8+i]
-#pragma unroll
-    for( int i = 0; i < 8; i++ )
-    {
-#define S( x ) d[i][x]
-#define D( x, v ) out[(x) * 8 + i] = sto<BD>( v )
-        DCT8_1D_ARR( S, D )
-#undef S
-#undef D
-    }
-}
-
-// QUANT_ONE, reference common/quant.c:50-57, branch-free: s = 0 for coef > 0,
-// -1 otherwise (coef == 0 takes the reference's negative branch too), so
-// |coef| = (coef ^ s) - s and the result is (q ^ s) - s.
-__device__ __forceinline__ int quant_one( int coef, uint32_t mf, uint32_t f )
-{
-    const int s = (coef > 0) - 1;
-    const uint32_t mag = (uint32_t)((coef ^ s) - s);
-    const int q = (int)(((f + mag) * mf) >> 16);
-    return (q ^ s) - s;
-}
-
-// k-th entry of a uniform mf / bias row, read as dwords so the loads are
-// scalar (s_load) even for the 16-bit tables of 8-bit depth
-template <typename U>
-__device__ __forceinline__ uint32_t urow( const U *__restrict__ p, int k )
-{
-    if constexpr( sizeof( U ) == 2 )
-    {
-        const uint32_t w = ((const uint32_t *)p)[k >> 1];
-        return (k & 1) ? w >> 16 : w & 0xffff;
-    }
-    else
-        return p[k];
-}
-
 template <typename T, int N>
 __device__ __forceinline__ void store_coefs( T *dst, const int (&v)[N] )
 {

@@ -702,3 +702,10 @@ hipError_t launch_deblock_frames( const x264hip_deblock_t *d, int mbw, int mbh, 
 hipError_t launch_deblock_strength( const x264hip_deblock_strength_t *s, int mbw, int mbh, int n_frames, uint8_t *bs,
                                     hipStream_t stream );
 } // namespace x264hip
+
+// the inter macroblock encode (mbenc.hip; include/x264hip_mbenc.h)
+struct x264hip_mbenc_t;
+namespace x264hip {
+template <int BD>
+hipError_t launch_mb_encode_inter( const x264hip_mbenc_t *e, int mbw, int mbh, int n_frames, hipStream_t stream );
+} // namespace x264hip

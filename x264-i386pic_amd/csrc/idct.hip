@@ -14,139 +14,13 @@
 //   decimate_score15/16/64, coeff_last*, coeff_level_run*   common/quant.c:318-398
 //   zigzag scans / sub / interleave              common/dct.c:768-940
 // Every dctcoef store of the reference (int16 at 8 bit) is reproduced with sto<BD>.
-#include "hipcommon.h"
+#include "txdev.h"
 
 #include <stdlib.h>
 
 namespace x264hip {
 
 // ------------------------------------------------------------------ helpers
-// read N pixels of a row at any alignment
-template <int BD, int N>
-__device__ __forceinline__ void read_row( const typename PT<BD>::pixel *p, int (&v)[N] )
-{
-    constexpr int PPD = PT<BD>::PPD;
-    uint32_t r[N / PPD];
-    load_packed<N / PPD>( p, r );
-#pragma unroll
-    for( int x = 0; x < N; x++ )
-        v[x] = upix<BD>( r[x / PPD], x % PPD );
-}
-
-// write N pixels of a row: packed dword stores when aligned, pixel stores otherwise
-template <int BD, int N>
-__device__ __forceinline__ void write_row( typename PT<BD>::pixel *p, const int (&v)[N] )
-{
-    constexpr int PPD = PT<BD>::PPD;
-    if( ((uintptr_t)p & 3) == 0 )
-    {
-#pragma unroll
-        for( int k = 0; k < N / PPD; k++ )
-        {
-            uint32_t w = 0;
-#pragma unroll
-            for( int j = 0; j < PPD; j++ )
-                w |= (uint32_t)v[k * PPD + j] << (j * (32 / PPD));
-            ((uint32_t *)p)[k] = w;
-        }
-    }
-    else
-    {
-#pragma unroll
-        for( int x = 0; x < N; x++ )
-            p[x] = (typename PT<BD>::pixel)v[x];
-    }
-}
-
-// residual of add4x4_idct: r[y][x] (dct.c:272-301, tmp and d stored as dctcoef)
-template <int BD>
-__device__ __forceinline__ void idct4_residual( const int (&c)[16], int (&r)[4][4] )
-{
-    int t[16];
-#pragma unroll
-    for( int i = 0; i < 4; i++ )
-    {
-        int s02 = c[0 * 4 + i] + c[2 * 4 + i], d02 = c[0 * 4 + i] - c[2 * 4 + i];
-        int s13 = c[1 * 4 + i] + (c[3 * 4 + i] >> 1), d13 = (c[1 * 4 + i] >> 1) - c[3 * 4 + i];
-        t[i * 4 + 0] = sto<BD>( s02 + s13 );
-        t[i * 4 + 1] = sto<BD>( d02 + d13 );
-        t[i * 4 + 2] = sto<BD>( d02 - d13 );
-        t[i * 4 + 3] = sto<BD>( s02 - s13 );
-    }
-#pragma unroll
-    for( int i = 0; i < 4; i++ )
-    {
-        int s02 = t[0 * 4 + i] + t[2 * 4 + i], d02 = t[0 * 4 + i] - t[2 * 4 + i];
-        int s13 = t[1 * 4 + i] + (t[3 * 4 + i] >> 1), d13 = (t[1 * 4 + i] >> 1) - t[3 * 4 + i];
-        r[0][i] = sto<BD>( (s02 + s13 + 32) >> 6 );
-        r[1][i] = sto<BD>( (d02 + d13 + 32) >> 6 );
-        r[2][i] = sto<BD>( (d02 - d13 + 32) >> 6 );
-        r[3][i] = sto<BD>( (s02 - s13 + 32) >> 6 );
-    }
-}
-
-// add a residual block to pred and store to dst (may alias pred)
-template <int BD, int N>
-__device__ __forceinline__ void add_block( const typename PT<BD>::pixel *pred, intptr_t ps, typename PT<BD>::pixel *dst,
-                                           intptr_t ds, const int (&r)[N][N] )
-{
-#pragma unroll
-    for( int y = 0; y < N; y++ )
-    {
-        int v[N];
-        read_row<BD, N>( pred + y * ps, v );
-#pragma unroll
-        for( int x = 0; x < N; x++ )
-            v[x] = clip_pix<BD>( v[x] + r[y][x] );
-        write_row<BD, N>( dst + y * ds, v );
-    }
-}
-
-// IDCT8_1D, dct.c:388-418
-#define IDCT8_1D( SRC, DST )                                                                   \
-    {                                                                                          \
-        int a0 = SRC( 0 ) + SRC( 4 ), a2 = SRC( 0 ) - SRC( 4 );                                \
-        int a4 = (SRC( 2 ) >> 1) - SRC( 6 ), a6 = (SRC( 6 ) >> 1) + SRC( 2 );                  \
-        int b0 = a0 + a6, b2 = a2 + a4, b4 = a2 - a4, b6 = a0 - a6;                            \
-        int a1 = -SRC( 3 ) + SRC( 5 ) - SRC( 7 ) - (SRC( 7 ) >> 1);                            \
-        int a3 = SRC( 1 ) + SRC( 7 ) - SRC( 3 ) - (SRC( 3 ) >> 1);                             \
-        int a5 = -SRC( 1 ) + SRC( 7 ) + SRC( 5 ) + (SRC( 5 ) >> 1);                            \
-        int a7 = SRC( 3 ) + SRC( 5 ) + SRC( 1 ) + (SRC( 1 ) >> 1);                             \
-        int b1 = (a7 >> 2) + a1, b3 = a3 + (a5 >> 2), b5 = (a3 >> 2) - a5, b7 = a7 - (a1 >> 2); \
-        DST( 0, b0 + b7 ); DST( 1, b2 + b5 ); DST( 2, b4 + b3 ); DST( 3, b6 + b1 );            \
-        DST( 4, b6 - b1 ); DST( 5, b4 - b3 ); DST( 6, b2 - b5 ); DST( 7, b0 - b7 );            \
-    }
-
-// residual of add8x8_idct8 (dct.c:420-440): c is modified as the reference does
-// in place (dc rounding and the column pass stored as dctcoef); r[row][col]
-template <int BD>
-__device__ __forceinline__ void idct8_residual( int (&c)[64], int (&r)[8][8] )
-{
-    c[0] = sto<BD>( c[0] + 32 );
-#pragma unroll
-    for( int i = 0; i < 8; i++ )
-    {
-#define SRC( x ) c[(x) * 8 + i]
-#define DST( x, v ) o[x] = sto<BD>( v )
-        int o[8];
-        IDCT8_1D( SRC, DST )
-#pragma unroll
-        for( int x = 0; x < 8; x++ )
-            c[x * 8 + i] = o[x];
-#undef SRC
-#undef DST
-    }
-#pragma unroll
-    for( int i = 0; i < 8; i++ )
-    {
-#define SRC( x ) c[i * 8 + (x)]
-#define DST( x, v ) r[x][i] = (v) >> 6
-        IDCT8_1D( SRC, DST )
-#undef SRC
-#undef DST
-    }
-}
-
 template <int BD, int N>
 __device__ __forceinline__ void load_coefs( const typename PT<BD>::dctcoef *p, int (&c)[N] )
 {
@@ -415,30 +289,6 @@ hipError_t launch_idct_dequant_2x4( int dconly, typename PT<BD>::dctcoef *dct, t
 
 // optimize_chroma_2x2_dc / 2x4_dc (quant.c:210-293): the reference's greedy
 // search, one lane per call; per-call dequant factor
-template <int NC>
-__device__ __forceinline__ void oc_idq( const int (&d)[NC], int dmf, int (&out)[NC] )
-{
-    if constexpr( NC == 8 )
-    {
-        int a0 = d[0] + d[1], a1 = d[2] + d[3], a2 = d[4] + d[5], a3 = d[6] + d[7];
-        int a4 = d[0] - d[1], a5 = d[2] - d[3], a6 = d[4] - d[5], a7 = d[6] - d[7];
-        int b0 = a0 + a1, b1 = a2 + a3, b2 = a4 + a5, b3 = a6 + a7;
-        int b4 = a0 - a1, b5 = a2 - a3, b6 = a4 - a5, b7 = a6 - a7;
-        const int v[8] = { b0 + b1, b2 + b3, b0 - b1, b2 - b3, b4 - b5, b6 - b7, b4 + b5, b6 + b7 };
-#pragma unroll
-        for( int k = 0; k < 8; k++ )
-            out[k] = (v[k] * dmf + 2080) >> 6;
-    }
-    else
-    {
-        int d0 = d[0] + d[1], d1 = d[2] + d[3], d2 = d[0] - d[1], d3 = d[2] - d[3];
-        out[0] = ((d0 + d1) * dmf >> 5) + 32;
-        out[1] = ((d0 - d1) * dmf >> 5) + 32;
-        out[2] = ((d2 + d3) * dmf >> 5) + 32;
-        out[3] = ((d2 - d3) * dmf >> 5) + 32;
-    }
-}
-
 template <int BD, int NC>
 __global__ __launch_bounds__( 256 ) void optimize_chroma_kernel( typename PT<BD>::dctcoef *dct, const int32_t *dmfs,
                                                                  int n, int32_t *nzo )
@@ -448,48 +298,18 @@ __global__ __launch_bounds__( 256 ) void optimize_chroma_kernel( typename PT<BD>
         return;
     typename PT<BD>::dctcoef *p = dct + (int64_t)i0 * NC;
     const int dmf = dmfs[i0];
-    int d[NC], orig[NC], out[NC];
+    int d[NC];
 #pragma unroll
     for( int k = 0; k < NC; k++ )
         d[k] = p[k];
-    oc_idq<NC>( d, dmf, orig );
-    int sum = 0;
-#pragma unroll
-    for( int k = 0; k < NC; k++ )
-        sum |= sto<BD>( orig[k] );
-    int nz = 0;
-    if( sum >> 6 )
+    const int nz = oc_search<BD, NC>( d, dmf );
+    if( nz >= 0 )
     {
-#pragma unroll
-        for( int k = 0; k < NC; k++ )
-            orig[k] = sto<BD>( orig[k] );
-#pragma unroll
-        for( int coeff = NC - 1; coeff >= 0; coeff-- )
-        {
-            int level = d[coeff];
-            const int sign = (level >> 31) | 1;
-            while( level )
-            {
-                d[coeff] = sto<BD>( level - sign );
-                oc_idq<NC>( d, dmf, out );
-                int diff = 0;
-#pragma unroll
-                for( int k = 0; k < NC; k++ )
-                    diff |= orig[k] ^ sto<BD>( out[k] );
-                if( diff >> 6 )
-                {
-                    nz = 1;
-                    d[coeff] = level;
-                    break;
-                }
-                level -= sign;
-            }
-        }
 #pragma unroll
         for( int k = 0; k < NC; k++ )
             p[k] = (typename PT<BD>::dctcoef)d[k];
     }
-    nzo[i0] = nz;
+    nzo[i0] = nz > 0;
 }
 
 template <int BD>
@@ -715,6 +535,16 @@ template <int FIELD> struct ZZ<4, FIELD>
     static constexpr int y( int i ) { return yx[FIELD][i][0]; }
     static constexpr int x( int i ) { return yx[FIELD][i][1]; }
 };
+
+// txdev.h's generated frame scans (the fused macroblock encode's) are these tables' frame halves
+template <int W> constexpr bool zigzag_walk_is_frame_scan()
+{
+    for( int i = 0; i < W * W; i++ )
+        if( ZZF<W>::y( i ) != ZZ<W, 0>::y( i ) || ZZF<W>::x( i ) != ZZ<W, 0>::x( i ) )
+            return false;
+    return true;
+}
+static_assert( zigzag_walk_is_frame_scan<4>() && zigzag_walk_is_frame_scan<8>(), "txdev.h: zigzag_frame_walk" );
 
 // zigzag_sub_4x4 / 4x4ac / 8x8 (dct.c:856-925), one lane per call
 template <int BD, int KIND, int FIELD>

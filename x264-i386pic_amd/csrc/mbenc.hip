@@ -1,0 +1,700 @@
+// The inter macroblock encode on gfx950 (include/x264hip_mbenc.h): the control flow of
+// macroblock_encode_internal (reference encoder/macroblock.c:618-972) and
+// mb_encode_chroma_internal (:259-490) for inter macroblocks over the transform cores of txdev.h.
+//
+// Mapping: 16 lanes per macroblock, four macroblocks per wave.  Luma, transform 4: lane l owns the
+// 4x4 block l of h->dct.luma4x4's order; transform 8: lanes 0..3 own the 8x8 blocks.  Chroma: lane
+// c < 4 (4:2:0) or < 8 (4:2:2) owns the 4x4 position c of BOTH channels, the 8 interleaved samples
+// of each of its rows, so that pixels move as whole dwords.  What the reference decides per 8x8,
+// per macroblock and per chroma channel (the decimate sums, the 2x2 / 2x4 DC blocks) is gathered
+// with ds_bpermute inside the macroblock's 16 lanes, and every lane then takes the decision
+// itself: all branches that hold a cross-lane read are uniform over a macroblock's lanes, so
+// macroblocks of different kinds (transform size, skip, intra) may share a wave.
+#include "txdev.h"
+#include "x264hip_mbenc.h"
+
+#include <string.h>
+
+namespace x264hip {
+
+// x264_lambda2_tab, reference common/tables.c:114-127 (pinned by tests/test_cpu_mbenc.py)
+__constant__ int c_lambda2_tab[82] = {
+    14, 18, 22, 28, 36, 45, 57, 72,
+    91, 115, 145, 182, 230, 290, 365, 460,
+    580, 731, 921, 1161, 1462, 1843, 2322, 2925,
+    3686, 4644, 5851, 7372, 9289, 11703, 14745, 18578,
+    23407, 29491, 37156, 46814, 58982, 74313, 93628, 117964,
+    148626, 187257, 235929, 297252, 374514, 471859, 594505, 749029,
+    943718, 1189010, 1498059, 1887436, 2378021, 2996119, 3774873, 4756042,
+    5992238, 7549747, 9512085, 11984476, 15099494, 19024170, 23968953, 30198988,
+    38048341, 47937906, 60397977, 76096683, 95875813, 120795955,
+    134217727, 134217727, 134217727, 134217727, 134217727, 134217727,
+    134217727, 134217727, 134217727, 134217727, 134217727, 134217727,
+};
+
+constexpr int CQM_4PY = 1, CQM_4PC = 3, CQM_8PY = 1;   // reference common/set.h
+
+// the launch's inputs, by value in the kernel arguments
+template <int BD> struct MbEncParams
+{
+    using pixel = typename PT<BD>::pixel;
+    using dctcoef = typename PT<BD>::dctcoef;
+    using udctcoef = typename PT<BD>::udctcoef;
+    const pixel *fenc, *fenc_c, *pred, *pred_c;
+    pixel *recon, *recon_c;
+    intptr_t fs, ffs, fcs, fcfs, ps, pfs, pcs, pcfs, rs, rfs, rcs, rcfs;
+    const udctcoef *q4mf, *q4b, *q8mf, *q8b;
+    const int32_t *dq4, *dq8;
+    const int8_t *qp;
+    const uint8_t *flags;
+    dctcoef *level, *chroma_dc;
+    uint8_t *nnz;
+    int32_t *cbp, *nz;
+    uint8_t *flags_out;
+    int mbw, mbh, nmb, dec, al;               // al: level and chroma_dc are 16-byte aligned
+    uint32_t cqp[16];                         // chroma_qp_table[0..63], four entries a word
+};
+
+// N coefficients to memory: 16-byte stores when the array is 16-byte aligned
+template <int BD, int N>
+__device__ __forceinline__ void put_coefs( typename PT<BD>::dctcoef *p, const int (&v)[N], bool al )
+{
+    if( al )
+    {
+        if constexpr( BD == 8 )
+        {
+#pragma unroll
+            for( int k = 0; k < N / 8; k++ )
+            {
+                uint32_t w[4];
+#pragma unroll
+                for( int j = 0; j < 4; j++ )
+                    w[j] = ((uint32_t)v[8 * k + 2 * j] & 0xffff) | ((uint32_t)v[8 * k + 2 * j + 1] << 16);
+                ((uint4 *)p)[k] = make_uint4( w[0], w[1], w[2], w[3] );
+            }
+        }
+        else
+        {
+#pragma unroll
+            for( int k = 0; k < N / 4; k++ )
+                ((int4 *)p)[k] = make_int4( v[4 * k], v[4 * k + 1], v[4 * k + 2], v[4 * k + 3] );
+        }
+    }
+    else
+    {
+#pragma unroll
+        for( int k = 0; k < N; k++ )
+            p[k] = (typename PT<BD>::dctcoef)v[k];
+    }
+}
+
+template <int N> __device__ __forceinline__ void zero( int (&v)[N] )
+{
+#pragma unroll
+    for( int k = 0; k < N; k++ )
+        v[k] = 0;
+}
+
+// v[j] of a register array for a per-lane j, without indexing registers by a lane value
+template <int N> __device__ __forceinline__ int pick( const int (&v)[N], int j )
+{
+    int r = 0;
+#pragma unroll
+    for( int k = 0; k < N; k++ )
+        r = j == k ? v[k] : r;
+    return r;
+}
+
+// the value of lane j of this macroblock's 16 lanes (every lane of the macroblock is active)
+__device__ __forceinline__ int mb_lane( int v, int j ) { return __shfl( v, j, 16 ); }
+
+// sum over the macroblock's 16 lanes
+__device__ __forceinline__ int mb_sum( int v )
+{
+#pragma unroll
+    for( int m = 1; m < 16; m <<= 1 )
+        v += __shfl_xor( v, m, 16 );
+    return v;
+}
+
+// ---- the static inlines of encoder/macroblock.c:35-96 and their 2x4 counterparts
+template <int NDC> __device__ __forceinline__ void zigzag_dc( const int (&dct)[NDC], int (&level)[8] )
+{
+    zero( level );
+    if constexpr( NDC == 4 )
+    {
+        level[0] = dct[0]; level[1] = dct[2]; level[2] = dct[1]; level[3] = dct[3];
+    }
+    else
+    {
+        level[0] = dct[0]; level[1] = dct[2]; level[2] = dct[1]; level[3] = dct[4];
+        level[4] = dct[6]; level[5] = dct[3]; level[6] = dct[5]; level[7] = dct[7];
+    }
+}
+
+// idct_dequant_2x2_dc / _dconly (macroblock.c:56-79) and idct_dequant_2x4_dc / _dconly
+// (quant.c:164-208): the value each 4x4 block's DC gets; dmf = dequant_mf[q % 6][0] << q / 6
+template <int BD, int NDC>
+__device__ __forceinline__ void idct_dequant_dc( const int (&dct)[NDC], int dmf, int (&out)[NDC] )
+{
+    if constexpr( NDC == 4 )
+    {
+        int o[4];
+        had2x2( dct, o );
+#pragma unroll
+        for( int k = 0; k < 4; k++ )
+            out[k] = sto<BD>( o[k] * dmf >> 5 );
+    }
+    else
+    {
+        int o[8];
+        had2x4( dct, o );
+#pragma unroll
+        for( int k = 0; k < 8; k++ )
+            out[k] = sto<BD>( (o[k] * dmf + 32) >> 6 );
+    }
+}
+
+// what one chroma channel leaves
+struct ChromaOut
+{
+    int res[4][4];      // this lane's residual
+    int lev[16];        // this lane's AC block in zigzag order (zeros when its nnz is 0)
+    int dc[8];          // h->dct.chroma_dc[ch] (zeros when its nnz is 0)
+    int nnz_ac, nnz_dc; // this lane's AC non_zero_count, the channel's DC non_zero_count
+    int ac;             // the channel took the DC + AC tail
+};
+
+// quant_2x2_dc (twice at 4:2:2) and, where `optimise`, mb_optimize_chroma_dc: 1 when a DC is coded
+template <int BD, int NDC>
+__device__ __forceinline__ int quant_chroma_dc( int (&dc)[NDC], uint32_t mf, uint32_t bias )
+{
+    int acc = 0;
+#pragma unroll
+    for( int k = 0; k < NDC; k++ )
+    {
+        dc[k] = sto<BD>( quant_one( dc[k], mf, bias ) );
+        acc |= dc[k];
+    }
+    return acc != 0;
+}
+
+template <int BD, int NDC> __device__ __forceinline__ int optimize_chroma_dc( int (&dc)[NDC], int dmf )
+{
+    if( dmf > 32 * 64 )                       // macroblock.c:250
+        return 1;
+    return oc_search<BD, NDC>( dc, dmf ) > 0;
+}
+
+// DC-only reconstruction: zigzag, idct_dequant_*_dconly, add8x8_idct_dc's value for this lane
+template <int BD, int NDC>
+__device__ __forceinline__ void chroma_dc_only( const int (&dc)[NDC], int dmf, int l, ChromaOut &o )
+{
+    o.nnz_dc = 1;
+    zigzag_dc<NDC>( dc, o.dc );
+    int v[NDC];
+    idct_dequant_dc<BD, NDC>( dc, dmf, v );
+    const int r = sto<BD>( (pick( v, l ) + 32) >> 6 );      // add8x8_idct_dc, dct.c:448-466
+#pragma unroll
+    for( int y = 0; y < 4; y++ )
+#pragma unroll
+        for( int x = 0; x < 4; x++ )
+            o.res[y][x] = r;
+}
+
+// One channel of mb_encode_chroma_internal.  d: this lane's 4x4 difference block (zeros on the
+// lanes past the channel's blocks); early / coded: the early termination was taken / this
+// channel's ssd is above its threshold.  Uniform over the macroblock's lanes except d and l.
+template <int BD, int CF>
+__device__ __forceinline__ void chroma_channel( const MbEncParams<BD> &a, int (&d)[4][4], int l, int qpc, bool early,
+                                                bool coded, ChromaOut &o )
+{
+    constexpr int NDC = CF == 1 ? 4 : 8;
+    constexpr int QP1 = 52 + 6 * (BD - 8);
+    const bool mine = l < NDC;
+    const int qdc = qpc + (CF == 2 ? 3 : 0);
+    const uint32_t dcmf = (uint32_t)a.q4mf[(CQM_4PC * QP1 + qdc) * 16] >> 1;
+    const uint32_t dcb = (uint32_t)a.q4b[(CQM_4PC * QP1 + qdc) * 16] << 1;
+    const int dmf = a.dq4[(CQM_4PC * 6 + qdc % 6) * 16] << (qdc / 6);
+#pragma unroll
+    for( int y = 0; y < 4; y++ )
+#pragma unroll
+        for( int x = 0; x < 4; x++ )
+            o.res[y][x] = 0;
+    zero( o.lev );
+    zero( o.dc );
+    o.nnz_ac = o.nnz_dc = o.ac = 0;
+    int dc[NDC];
+    if( early )
+    {
+        if( !coded )
+            return;
+        // sub8x8_dct_dc / sub8x16_dct_dc (dct.c:207-270): the 4x4 sums, then the butterflies
+        int t = 0;
+#pragma unroll
+        for( int y = 0; y < 4; y++ )
+#pragma unroll
+            for( int x = 0; x < 4; x++ )
+                t += d[y][x];
+        int s[NDC];
+#pragma unroll
+        for( int k = 0; k < NDC; k++ )
+            s[k] = CF == 1 ? sto<BD>( mb_lane( t, k ) ) : mb_lane( t, k );
+        if constexpr( CF == 1 )
+            had2x2( s, dc );
+        else
+            had2x4( s, dc );
+#pragma unroll
+        for( int k = 0; k < NDC; k++ )
+            dc[k] = sto<BD>( dc[k] );
+        if( quant_chroma_dc<BD, NDC>( dc, dcmf, dcb ) && optimize_chroma_dc<BD, NDC>( dc, dmf ) )
+            chroma_dc_only<BD, NDC>( dc, dmf, l, o );
+        return;
+    }
+    // sub8x8_dct, dct2x2dc / dct2x4dc
+    int c[16];
+    dct4x4_core<BD>( d, c );
+    int g[NDC];
+#pragma unroll
+    for( int k = 0; k < NDC; k++ )
+        g[k] = mb_lane( c[0], k );
+    if constexpr( CF == 1 )
+        had2x2( g, dc );
+    else
+        had2x4( g, dc );
+#pragma unroll
+    for( int k = 0; k < NDC; k++ )
+        dc[k] = sto<BD>( dc[k] );
+    c[0] = 0;
+    // quant_4x4x4, decimate_score15 while the score is < 7
+    const typename PT<BD>::udctcoef *mf = a.q4mf + (CQM_4PC * QP1 + qpc) * 16, *bias = a.q4b + (CQM_4PC * QP1 + qpc) * 16;
+    int acc = 0;
+#pragma unroll
+    for( int k = 0; k < 16; k++ )
+    {
+        c[k] = sto<BD>( quant_one( c[k], mf[k], bias[k] ) );
+        acc |= c[k];
+    }
+    const int nzb = mine && acc != 0;
+    int score = 0;
+    if( a.dec && nzb )
+        score = decimate_score<16, 1>( [&]( int i ) { return c[ZZF<4>::x( i ) * 4 + ZZF<4>::y( i )]; } );
+    int i_decimate_score = a.dec ? 0 : 7, nz_ac = 0;
+#pragma unroll
+    for( int k = 0; k < NDC; k++ )
+    {
+        const int nzk = mb_lane( nzb, k ), sk = mb_lane( score, k );
+        if( nzk )
+        {
+            nz_ac = 1;
+            if( i_decimate_score < 7 )
+                i_decimate_score += sk;
+        }
+    }
+    const int nz_dc = quant_chroma_dc<BD, NDC>( dc, dcmf, dcb );
+    if( i_decimate_score < 7 || !nz_ac )
+    {
+        // decimated: DC-only through mb_optimize_chroma_dc, or empty
+        if( nz_dc && optimize_chroma_dc<BD, NDC>( dc, dmf ) )
+            chroma_dc_only<BD, NDC>( dc, dmf, l, o );
+        return;
+    }
+    // DC + AC
+    o.ac = 1;
+    o.nnz_ac = nzb;
+    o.nnz_dc = nz_dc;
+    if( nzb )
+    {
+#pragma unroll
+        for( int i = 0; i < 16; i++ )
+            o.lev[i] = c[ZZF<4>::x( i ) * 4 + ZZF<4>::y( i )];
+        const int32_t *m = a.dq4 + (CQM_4PC * 6 + qpc % 6) * 16;
+        const int qb = qpc / 6 - 4;
+#pragma unroll
+        for( int k = 0; k < 16; k++ )
+            c[k] = sto<BD>( dequant_one( c[k], m[k], qb ) );
+    }
+    if( nz_dc )
+    {
+        zigzag_dc<NDC>( dc, o.dc );
+        int v[NDC];
+        idct_dequant_dc<BD, NDC>( dc, dmf, v );
+        c[0] = pick( v, l );
+    }
+    if( mine )
+        idct4_residual<BD>( c, o.res );
+}
+
+template <int BD, int CF>
+__global__ __launch_bounds__( 256 ) void mb_encode_inter_kernel( const MbEncParams<BD> a )
+{
+    using pixel = typename PT<BD>::pixel;
+    using dctcoef = typename PT<BD>::dctcoef;
+    constexpr int QP1 = 52 + 6 * (BD - 8);
+    // the chroma qp table, indexed per lane below
+    __shared__ uint32_t s_cqp[16];
+#pragma unroll
+    for( int k = 0; k < 16; k++ )
+        if( threadIdx.x == k )
+            s_cqp[k] = a.cqp[k];
+    __syncthreads();
+    const int l = threadIdx.x & 15;
+    const int slot = (threadIdx.x & 63) >> 4;                  // the macroblock's place in its wave
+    const int mb = blockIdx.x * 16 + (threadIdx.x >> 4);
+    if( mb >= a.nmb )
+        return;
+    const int fl = a.flags[mb];
+    if( fl & X264HIP_MBENC_INTRA )
+    {
+        if( l == 0 )
+            a.flags_out[mb] = (uint8_t)fl;
+        return;
+    }
+    const int per = a.mbw * a.mbh;
+    const int f = mb / per, rem = mb - f * per;
+    const int mby = rem / a.mbw, mbx = rem - mby * a.mbw;
+    const int qp = min( max( (int)a.qp[mb], 0 ), QP1 - 1 );
+    const bool skip = fl & X264HIP_MBENC_SKIP;
+    const bool t8 = (fl & X264HIP_MBENC_T8x8) && a.q8mf;
+    const bool al = a.al;
+    dctcoef *lvl = a.level + (int64_t)mb * (48 * 16);
+
+    // ---------------------------------------------------------------- luma
+    int lmask = 0;                             // non_zero_count of the 16 luma blocks, bit = block index
+    int k4 = 0;                                // transform 8: the kept 8x8 blocks
+    if( !t8 )
+    {
+        const int i8 = l >> 2, i4 = l & 3;
+        const int x = (i8 & 1) * 8 + (i4 & 1) * 4, y = (i8 >> 1) * 8 + (i4 >> 1) * 4;
+        const pixel *fp = a.fenc + (intptr_t)f * a.ffs + (intptr_t)(16 * mby + y) * a.fs + 16 * mbx + x;
+        const pixel *pp = a.pred + (intptr_t)f * a.pfs + (intptr_t)(16 * mby + y) * a.ps + 16 * mbx + x;
+        pixel *rp = a.recon + (intptr_t)f * a.rfs + (intptr_t)(16 * mby + y) * a.rs + 16 * mbx + x;
+        int c[16];
+        zero( c );
+        int nzb = 0, score = 0;
+        if( !skip )
+        {
+            int d[4][4];
+            load_diff<BD, 4>( d, fp, a.fs, pp, a.ps );
+            dct4x4_core<BD>( d, c );
+            const typename PT<BD>::udctcoef *mf = a.q4mf + (CQM_4PY * QP1 + qp) * 16, *bias = a.q4b + (CQM_4PY * QP1 + qp) * 16;
+            int acc = 0;
+#pragma unroll
+            for( int k = 0; k < 16; k++ )
+            {
+                c[k] = sto<BD>( quant_one( c[k], mf[k], bias[k] ) );
+                acc |= c[k];
+            }
+            nzb = acc != 0;
+            if( a.dec && nzb )
+                score = decimate_score<16, 0>( [&]( int i ) { return c[ZZF<4>::x( i ) * 4 + ZZF<4>::y( i )]; } );
+        }
+        // the 8x8's decision (macroblock.c:862-905), taken by each of its four lanes
+        int i_decimate_8x8 = a.dec ? 0 : 6, nnz8x8 = 0;
+#pragma unroll
+        for( int k = 0; k < 4; k++ )
+        {
+            const int nzk = mb_lane( nzb, (l & 12) + k ), sk = mb_lane( score, (l & 12) + k );
+            if( nzk )
+            {
+                nnz8x8 = 1;
+                if( i_decimate_8x8 < 6 )
+                    i_decimate_8x8 += sk;
+            }
+        }
+        const int contrib = nnz8x8 ? i_decimate_8x8 : 0;
+        int i_decimate_mb = 0;
+#pragma unroll
+        for( int k = 0; k < 4; k++ )
+            i_decimate_mb += mb_lane( contrib, 4 * k );
+        const bool keep = nnz8x8 && i_decimate_8x8 >= 4 && i_decimate_mb >= 6;
+        const bool nn = keep && nzb;
+        int lev[16], res[4][4];
+        zero( lev );
+#pragma unroll
+        for( int yy = 0; yy < 4; yy++ )
+#pragma unroll
+            for( int xx = 0; xx < 4; xx++ )
+                res[yy][xx] = 0;
+        if( nn )
+        {
+#pragma unroll
+            for( int i = 0; i < 16; i++ )
+                lev[i] = c[ZZF<4>::x( i ) * 4 + ZZF<4>::y( i )];
+            const int32_t *m = a.dq4 + (CQM_4PY * 6 + qp % 6) * 16;
+            const int qb = qp / 6 - 4;
+#pragma unroll
+            for( int k = 0; k < 16; k++ )
+                c[k] = sto<BD>( dequant_one( c[k], m[k], qb ) );
+            idct4_residual<BD>( c, res );
+        }
+        put_coefs<BD, 16>( lvl + l * 16, lev, al );
+        add_block<BD, 4>( pp, a.ps, rp, a.rs, res );
+        lmask = (int)((__ballot( nn ) >> (16 * slot)) & 0xffff);
+    }
+    else
+    {
+        const int x = (l & 1) * 8, y = ((l >> 1) & 1) * 8;
+        const pixel *fp = a.fenc + (intptr_t)f * a.ffs + (intptr_t)(16 * mby + y) * a.fs + 16 * mbx + x;
+        const pixel *pp = a.pred + (intptr_t)f * a.pfs + (intptr_t)(16 * mby + y) * a.ps + 16 * mbx + x;
+        pixel *rp = a.recon + (intptr_t)f * a.rfs + (intptr_t)(16 * mby + y) * a.rs + 16 * mbx + x;
+        int c[64];
+        zero( c );
+        int nzb = 0, score = 0;
+        if( l < 4 && !skip )
+        {
+            int d[8][8];
+            load_diff<BD, 8>( d, fp, a.fs, pp, a.ps );
+            dct8x8_core<BD>( d, c );
+            const typename PT<BD>::udctcoef *mf = a.q8mf + (CQM_8PY * QP1 + qp) * 64, *bias = a.q8b + (CQM_8PY * QP1 + qp) * 64;
+            int acc = 0;
+#pragma unroll
+            for( int k = 0; k < 64; k++ )
+            {
+                c[k] = sto<BD>( quant_one( c[k], mf[k], bias[k] ) );
+                acc |= c[k];
+            }
+            nzb = acc != 0;
+            if( a.dec && nzb )
+                score = decimate_score<64, 0>( [&]( int i ) { return c[ZZF<8>::x( i ) * 8 + ZZF<8>::y( i )]; } );
+        }
+        // macroblock.c:813-842
+        int i_decimate_mb = 0;
+#pragma unroll
+        for( int k = 0; k < 4; k++ )
+        {
+            const int nzk = mb_lane( nzb, k ), sk = mb_lane( score, k );
+            if( a.dec && nzk )
+                i_decimate_mb += sk;
+        }
+        const bool keep = nzb && (!a.dec || (score >= 4 && i_decimate_mb >= 6));
+        if( l < 4 )
+        {
+            int lev[64];
+            zero( lev );
+            if( keep )
+            {
+#pragma unroll
+                for( int i = 0; i < 64; i++ )
+                    lev[i] = c[ZZF<8>::x( i ) * 8 + ZZF<8>::y( i )];
+            }
+            put_coefs<BD, 64>( lvl + l * 64, lev, al );
+            int res[8][8];
+            if( keep )
+            {
+                const int32_t *m = a.dq8 + (CQM_8PY * 6 + qp % 6) * 64;
+                const int qb = qp / 6 - 6;
+#pragma unroll
+                for( int k = 0; k < 64; k++ )
+                    c[k] = sto<BD>( dequant_one( c[k], m[k], qb ) );
+                idct8_residual<BD>( c, res );
+            }
+            else
+            {
+#pragma unroll
+                for( int yy = 0; yy < 8; yy++ )
+#pragma unroll
+                    for( int xx = 0; xx < 8; xx++ )
+                        res[yy][xx] = 0;
+            }
+            add_block<BD, 8>( pp, a.ps, rp, a.rs, res );
+        }
+        k4 = (int)((__ballot( keep && l < 4 ) >> (16 * slot)) & 0xf);
+#pragma unroll
+        for( int k = 0; k < 4; k++ )
+            lmask |= ((k4 >> k) & 1) * (0xf << (4 * k));
+    }
+    int cbp_luma = k4;
+    if( !t8 )
+#pragma unroll
+        for( int k = 0; k < 4; k++ )
+            cbp_luma |= (((lmask >> (4 * k)) & 0xf) != 0) << k;
+
+    // ---------------------------------------------------------------- chroma
+    int cbp_chroma = 0, nnz_dc0 = 0, nnz_dc1 = 0, acm0 = 0, acm1 = 0;
+    int dco[2][8];
+    zero( dco[0] );
+    zero( dco[1] );
+    if constexpr( CF != 0 )
+    {
+        constexpr int NCB = CF == 1 ? 4 : 8, CH = CF == 1 ? 8 : 16;
+        const bool mine = l < NCB;
+        const int bx = l & 1, by = (l >> 1) & 3;
+        const pixel *fp = a.fenc_c + (intptr_t)f * a.fcfs + (intptr_t)(CH * mby + 4 * by) * a.fcs + 16 * mbx + 8 * bx;
+        const pixel *pp = a.pred_c + (intptr_t)f * a.pcfs + (intptr_t)(CH * mby + 4 * by) * a.pcs + 16 * mbx + 8 * bx;
+        pixel *rp = a.recon_c + (intptr_t)f * a.rcfs + (intptr_t)(CH * mby + 4 * by) * a.rcs + 16 * mbx + 8 * bx;
+        ChromaOut u, v;
+        int du[4][4], dv[4][4];
+#pragma unroll
+        for( int y = 0; y < 4; y++ )
+#pragma unroll
+            for( int x = 0; x < 4; x++ )
+                du[y][x] = dv[y][x] = 0;
+        if( mine && !skip )
+        {
+#pragma unroll
+            for( int y = 0; y < 4; y++ )
+            {
+                int e[8], p[8];
+                read_row<BD, 8>( fp + y * a.fcs, e );
+                read_row<BD, 8>( pp + y * a.pcs, p );
+#pragma unroll
+                for( int x = 0; x < 4; x++ )
+                {
+                    du[y][x] = e[2 * x] - p[2 * x];
+                    dv[y][x] = e[2 * x + 1] - p[2 * x + 1];
+                }
+            }
+        }
+        if( !skip )
+        {
+            const int qpc = min( (int)((s_cqp[qp >> 2] >> (8 * (qp & 3))) & 255), QP1 - 1 - (CF == 2 ? 3 : 0) );
+            // the early termination (macroblock.c:283-341): pixel_var2_8x8 / 8x16, pixel.c:206-231
+            bool early = false, coded_u = false, coded_v = false;
+            if( a.dec && qpc >= 18 )
+            {
+                int su = 0, sv = 0, qu = 0, qv = 0;
+#pragma unroll
+                for( int y = 0; y < 4; y++ )
+#pragma unroll
+                    for( int x = 0; x < 4; x++ )
+                    {
+                        su += du[y][x]; qu += du[y][x] * du[y][x];
+                        sv += dv[y][x]; qv += dv[y][x] * dv[y][x];
+                    }
+                su = mb_sum( su ); sv = mb_sum( sv ); qu = mb_sum( qu ); qv = mb_sum( qv );
+                constexpr int SHIFT = CF == 1 ? 6 : 7;
+                const int thresh = CF == 2 ? (c_lambda2_tab[qpc] + 16) >> 5 : (c_lambda2_tab[qpc] + 32) >> 6;
+                const int var2 = (int)( qu - ((int64_t)su * su >> SHIFT) + qv - ((int64_t)sv * sv >> SHIFT) );
+                early = var2 < thresh * 4;
+                coded_u = qu > thresh;
+                coded_v = qv > thresh;
+            }
+            chroma_channel<BD, CF>( a, du, l, qpc, early, coded_u, u );
+            chroma_channel<BD, CF>( a, dv, l, qpc, early, coded_v, v );
+            nnz_dc0 = u.nnz_dc; nnz_dc1 = v.nnz_dc;
+            if( early )
+                cbp_chroma = nnz_dc0 | nnz_dc1;
+            else
+            {
+                const int t = u.ac | v.ac;                          // macroblock.c:487-489
+                cbp_chroma = t + (nnz_dc0 | nnz_dc1 | t);
+            }
+#pragma unroll
+            for( int k = 0; k < 8; k++ )
+            {
+                dco[0][k] = u.dc[k];
+                dco[1][k] = v.dc[k];
+            }
+        }
+        else
+        {
+#pragma unroll
+            for( int y = 0; y < 4; y++ )
+#pragma unroll
+                for( int x = 0; x < 4; x++ )
+                    u.res[y][x] = v.res[y][x] = 0;
+            zero( u.lev );
+            zero( v.lev );
+            u.nnz_ac = v.nnz_ac = 0;
+        }
+        if( mine )
+        {
+#pragma unroll
+            for( int y = 0; y < 4; y++ )
+            {
+                int p[8];
+                read_row<BD, 8>( pp + y * a.pcs, p );
+#pragma unroll
+                for( int x = 0; x < 4; x++ )
+                {
+                    p[2 * x] = clip_pix<BD>( p[2 * x] + u.res[y][x] );
+                    p[2 * x + 1] = clip_pix<BD>( p[2 * x + 1] + v.res[y][x] );
+                }
+                write_row<BD, 8>( rp + y * a.rcs, p );
+            }
+            const int blk = 16 + (l >> 2) * 8 + (l & 3);
+            put_coefs<BD, 16>( lvl + blk * 16, u.lev, al );
+            put_coefs<BD, 16>( lvl + (blk + 16) * 16, v.lev, al );
+        }
+        acm0 = (int)((__ballot( mine && u.nnz_ac ) >> (16 * slot)) & 0xff);
+        acm1 = (int)((__ballot( mine && v.nnz_ac ) >> (16 * slot)) & 0xff);
+    }
+
+    // ---------------------------------------------------------------- the per-macroblock outputs
+    // block 16 + l (and 32 + l): a chroma AC block of this format, owned by chroma lane `owner`?
+    const bool cblk = CF == 1 ? l < 4 : CF == 2 ? !(l & 4) : false;
+    const int owner = (l >> 3) * 4 + (l & 3);
+    if( !cblk )
+    {
+        int z[16];
+        zero( z );
+        put_coefs<BD, 16>( lvl + (16 + l) * 16, z, al );
+        put_coefs<BD, 16>( lvl + (32 + l) * 16, z, al );
+    }
+    uint8_t *nn = a.nnz + (int64_t)mb * 48;
+    nn[l] = (uint8_t)((lmask >> l) & 1);
+    nn[16 + l] = (uint8_t)(cblk ? (acm0 >> owner) & 1 : 0);
+    nn[32 + l] = (uint8_t)(cblk ? (acm1 >> owner) & 1 : 0);
+    if( l < 2 )
+    {
+        int o[8];
+#pragma unroll
+        for( int k = 0; k < 8; k++ )
+            o[k] = l ? dco[1][k] : dco[0][k];
+        put_coefs<BD, 8>( a.chroma_dc + (int64_t)mb * 16 + l * 8, o, al );
+    }
+    if( l == 0 )
+    {
+        const int cbp = cbp_chroma << 4 | cbp_luma | nnz_dc0 << 9 | nnz_dc1 << 10;
+        a.cbp[mb] = cbp;
+        a.nz[mb] = t8 ? k4 : lmask;
+        a.flags_out[mb] = (uint8_t)((fl & 3) | ((fl & X264HIP_MBENC_D16x16) && !cbp ? X264HIP_MBENC_D16x16 : 0));
+    }
+}
+
+// the arguments were checked by the C entry (capi.cpp x264hip_*_mb_encode_inter)
+template <int BD>
+hipError_t launch_mb_encode_inter( const x264hip_mbenc_t *e, int mbw, int mbh, int n_frames, hipStream_t stream )
+{
+    using pixel = typename PT<BD>::pixel;
+    using dctcoef = typename PT<BD>::dctcoef;
+    using udctcoef = typename PT<BD>::udctcoef;
+    const int64_t nmb = (int64_t)n_frames * mbw * mbh;
+    if( !e || nmb <= 0 )
+        return hipSuccess;
+    constexpr int QP_MAX_SPEC = 51 + 6 * (BD - 8);
+    MbEncParams<BD> a;
+    a.fenc = (const pixel *)e->fenc; a.fenc_c = (const pixel *)e->fenc_chroma;
+    a.pred = (const pixel *)e->pred; a.pred_c = (const pixel *)e->pred_chroma;
+    a.recon = (pixel *)e->recon; a.recon_c = (pixel *)e->recon_chroma;
+    a.fs = e->fenc_stride; a.ffs = e->fenc_frame_stride;
+    a.fcs = e->fenc_chroma_stride; a.fcfs = e->fenc_chroma_frame_stride;
+    a.ps = e->pred_stride; a.pfs = e->pred_frame_stride;
+    a.pcs = e->pred_chroma_stride; a.pcfs = e->pred_chroma_frame_stride;
+    a.rs = e->recon_stride; a.rfs = e->recon_frame_stride;
+    a.rcs = e->recon_chroma_stride; a.rcfs = e->recon_chroma_frame_stride;
+    a.q4mf = (const udctcoef *)e->quant4_mf; a.q4b = (const udctcoef *)e->quant4_bias;
+    a.q8mf = (const udctcoef *)e->quant8_mf; a.q8b = (const udctcoef *)e->quant8_bias;
+    a.dq4 = e->dequant4_mf; a.dq8 = e->dequant8_mf;
+    a.qp = e->qp; a.flags = e->mb_flags;
+    a.level = (dctcoef *)e->level; a.chroma_dc = (dctcoef *)e->chroma_dc;
+    a.nnz = e->nnz; a.cbp = e->cbp; a.nz = e->nz; a.flags_out = e->flags_out;
+    a.mbw = mbw; a.mbh = mbh; a.nmb = (int)nmb;
+    a.dec = e->b_dct_decimate != 0;
+    a.al = !(((uintptr_t)e->level | (uintptr_t)e->chroma_dc) & 15);
+    uint8_t cqp[64] = { 0 };
+    memcpy( cqp, e->chroma_qp_table, QP_MAX_SPEC + 1 );
+    memcpy( a.cqp, cqp, sizeof( cqp ) );
+    const dim3 grid( (unsigned)((nmb + 15) / 16) ), blk( 256 );
+    switch( e->chroma_format )
+    {
+        case 0: hipLaunchKernelGGL( ( mb_encode_inter_kernel<BD, 0> ), grid, blk, 0, stream, a ); break;
+        case 1: hipLaunchKernelGGL( ( mb_encode_inter_kernel<BD, 1> ), grid, blk, 0, stream, a ); break;
+        default: hipLaunchKernelGGL( ( mb_encode_inter_kernel<BD, 2> ), grid, blk, 0, stream, a ); break;
+    }
+    return hipGetLastError();
+}
+X264HIP_INSTANTIATE( launch_mb_encode_inter );
+
+} // namespace x264hip
