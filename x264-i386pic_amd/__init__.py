@@ -34,6 +34,7 @@ __all__ = [
     "mb_mc", "Mc",
     "deblock_strength", "deblock_frames", "chroma_qp_table", "Deblock", "DeblockStrength",
     "mb_encode_inter", "MbEnc", "MBENC_INTRA", "MBENC_T8x8", "MBENC_D16x16", "MBENC_SKIP", "MBENC_OUTPUTS",
+    "mb_encode_intra", "MbIntra", "MBINTRA_I16x16", "MBINTRA_OUTPUTS",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -339,7 +340,7 @@ def cqm_dequant(scaling_lists, transform_8x8=True):
 
 # ----------------------------------------------------------------- declarations
 # Every function of include/x264hip.h, include/x264hip_mbtree.h, include/x264hip_mc.h,
-# include/x264hip_deblock.h and include/x264hip_mbenc.h, once:
+# include/x264hip_deblock.h, include/x264hip_mbenc.h and include/x264hip_mbintra.h, once:
 # "return:parameters", one letter each, in the struct module's spelling where it has one.
 # tests/test_abi.py checks the first two tables against x264hip.h's prototypes,
 # tests/test_cpu_mbtree.py the third against x264hip_mbtree.h's, tests/test_cpu_mc.py the fourth
@@ -466,6 +467,11 @@ _DEBLOCK_PLAIN = {
 _MBENC = {
     "mb_encode_inter": "i:PiiiP",
 }
+# include/x264hip_mbintra.h: x264hip_8_<name> and x264hip_10_<name> (tests/test_cpu_mbintra.py
+# checks them against the header's prototypes)
+_MBINTRA = {
+    "mb_encode_intra": "i:PiiiP",
+}
 
 
 def _declare(L):
@@ -489,6 +495,9 @@ def _declare(L):
     for name, sig in _DEBLOCK_PLAIN.items():
         declare(getattr(L, f"x264hip_{name}"), sig)
     for name, sig in _MBENC.items():
+        for bd in (8, 10):
+            declare(getattr(L, f"x264hip_{bd}_{name}"), sig)
+    for name, sig in _MBINTRA.items():
         for bd in (8, 10):
             declare(getattr(L, f"x264hip_{bd}_{name}"), sig)
 
@@ -1448,6 +1457,103 @@ def mb_encode_inter(fenc, pred, mb_width, mb_height, nframes, qp, mb_flags, quan
         setattr(e, name, _ptr(out[name]).value or dummy)
     fname = f"x264hip_{bd}_mb_encode_inter"
     _rc(getattr(lib(), fname)(_c.byref(e), mb_width, mb_height, nframes, _stream()), fname)
+    out["recon"], out["recon_chroma"] = recon, recon_chroma if cf else None
+    return out
+
+
+# ----------------------------------------------------------------- intra MB encode (include/x264hip_mbintra.h)
+MBINTRA_I16x16 = 16
+
+
+class MbIntra(_c.Structure):
+    """x264hip_mbintra_t"""
+    _fields_ = [("chroma_format", _c.c_int32), ("b_dct_decimate", _c.c_int32), ("chroma_qp_table", _P),
+                ("quant4_mf", _P), ("quant4_bias", _P), ("quant8_mf", _P), ("quant8_bias", _P),
+                ("dequant4_mf", _P), ("dequant8_mf", _P),
+                ("fenc", _P), ("fenc_stride", _IP), ("fenc_frame_stride", _IP),
+                ("fenc_chroma", _P), ("fenc_chroma_stride", _IP), ("fenc_chroma_frame_stride", _IP),
+                ("recon", _P), ("recon_stride", _IP), ("recon_frame_stride", _IP),
+                ("recon_chroma", _P), ("recon_chroma_stride", _IP), ("recon_chroma_frame_stride", _IP),
+                ("qp", _P), ("mb_flags", _P), ("pred_mode", _P), ("chroma_pred_mode", _P),
+                ("level", _P), ("chroma_dc", _P), ("nnz", _P), ("cbp", _P), ("nz", _P), ("flags_out", _P),
+                ("luma_dc", _P)]
+
+
+MBINTRA_OUTPUTS = MBENC_OUTPUTS + ("luma_dc",)
+
+
+def mb_encode_intra(fenc, recon, mb_width, mb_height, nframes, qp, mb_flags, pred_mode, quant4, dequant4_mf,
+                    quant8=None, dequant8_mf=None, chroma_format=0, fenc_chroma=None, recon_chroma=None,
+                    chroma_pred_mode=None, b_dct_decimate=1, qp_table=None, outs=None, stream=None):
+    """x264_macroblock_encode of every intra macroblock (I_16x16 / I_4x4 / I_8x8, modes given) of
+    nframes frames (x264hip_*_mb_encode_intra, include/x264hip_mbintra.h), after mb_encode_inter on
+    the same recon planes and before deblocking.  Planes, qp, the tables and qp_table as
+    mb_encode_inter; recon / recon_chroma are read (the neighbours) and written (the intra
+    macroblocks).  mb_flags uint8 [mbs]: MBENC_INTRA marks the macroblocks of this call, with
+    MBENC_T8x8 I_8x8, else with MBINTRA_I16x16 I_16x16, else I_4x4.  pred_mode int8 [mbs][16] and
+    chroma_pred_mode int8 [mbs]: x264's mode numbers.  outs: {name: tensor} for any of
+    MBINTRA_OUTPUTS to write into, for instance the dict mb_encode_inter returned (the two calls
+    fill disjoint macroblocks); the others are allocated zeroed.  stream: a torch.cuda.Stream, default
+    the current one.  Returns a dict: recon, recon_chroma (the plane tuples) and MBINTRA_OUTPUTS."""
+    import torch
+    bd = _pix_bd(recon[0])
+    cf = int(chroma_format)
+    if cf not in (0, 1, 2):
+        raise ValueError("mb_encode_intra: chroma_format is 0 (luma only), 1 (4:2:0) or 2 (4:2:2)")
+    if cf and (fenc_chroma is None or recon_chroma is None or chroma_pred_mode is None):
+        raise ValueError("mb_encode_intra: the chroma format needs fenc_chroma, recon_chroma and chroma_pred_mode")
+    if (quant8 is None) != (dequant8_mf is None):
+        raise ValueError("mb_encode_intra: quant8 and dequant8_mf come together")
+    if mb_width < 0 or mb_height < 0 or nframes < 0:
+        raise ValueError("mb_encode_intra: negative size")
+    table = chroma_qp_table(bd) if qp_table is None else np.ascontiguousarray(np.asarray(qp_table, np.uint8))
+    if table.size < 52 + 6 * (bd - 8):
+        raise ValueError("mb_encode_intra: the chroma qp table needs QP_MAX_SPEC + 1 entries")
+    nmb = nframes * mb_width * mb_height
+    if qp.numel() < nmb or mb_flags.numel() < nmb:
+        raise ValueError("mb_encode_intra: qp and mb_flags need one element per macroblock")
+    if pred_mode.dtype != torch.int8 or pred_mode.numel() < 16 * nmb or not pred_mode.is_contiguous():
+        raise ValueError("mb_encode_intra: pred_mode must be a contiguous int8 tensor of 16 modes per macroblock")
+    if cf and (chroma_pred_mode.dtype != torch.int8 or chroma_pred_mode.numel() < nmb
+               or not chroma_pred_mode.is_contiguous()):
+        raise ValueError("mb_encode_intra: chroma_pred_mode must be a contiguous int8 tensor of one mode per macroblock")
+    cdt = torch.int16 if bd == 8 else torch.int32
+    shapes = {"level": ((nmb, 48, 16), cdt), "chroma_dc": ((nmb, 2, 8), cdt), "nnz": ((nmb, 48), torch.uint8),
+              "cbp": ((nmb,), torch.int32), "nz": ((nmb,), torch.int32), "flags_out": ((nmb,), torch.uint8),
+              "luma_dc": ((nmb, 16), cdt)}
+    out = {k: v for k, v in (outs or {}).items() if k in shapes}
+    for name, (shape, dt) in shapes.items():
+        if name not in out:
+            out[name] = torch.zeros(shape, dtype=dt, device=recon[0].device)
+        elif out[name].dtype != dt or out[name].numel() < int(np.prod(shape)) or not out[name].is_contiguous():
+            raise ValueError(f"mb_encode_intra: {name} must be a contiguous {dt} tensor of {shape}")
+    e = MbIntra()
+    e.chroma_format, e.b_dct_decimate = cf, int(bool(b_dct_decimate))
+    e.chroma_qp_table = table.ctypes.data
+    e.quant4_mf, e.quant4_bias, e.dequant4_mf = _ptr(quant4[0]).value, _ptr(quant4[1]).value, _ptr(dequant4_mf).value
+    if quant8 is not None:
+        e.quant8_mf, e.quant8_bias, e.dequant8_mf = _ptr(quant8[0]).value, _ptr(quant8[1]).value, _ptr(dequant8_mf).value
+    planes = [("fenc", fenc), ("recon", recon)]
+    if cf:
+        planes += [("fenc_chroma", fenc_chroma), ("recon_chroma", recon_chroma)]
+    for name, (t, origin, stride, fstride) in planes:
+        if _pix_bd(t) != bd:
+            raise TypeError("mb_encode_intra: the planes disagree on the bit depth")
+        setattr(e, name, _ptr(t, origin).value)
+        setattr(e, name + "_stride", stride)
+        setattr(e, name + "_frame_stride", fstride)
+    # (torch gives an empty tensor a NULL pointer; with no macroblock the arrays are not read)
+    dummy = _c.addressof(e)
+    e.qp = _ptr(qp).value or dummy
+    e.mb_flags = _ptr(mb_flags).value or dummy
+    e.pred_mode = _ptr(pred_mode).value or dummy
+    if cf:
+        e.chroma_pred_mode = _ptr(chroma_pred_mode).value or dummy
+    for name in MBINTRA_OUTPUTS:
+        setattr(e, name, _ptr(out[name]).value or dummy)
+    fname = f"x264hip_{bd}_mb_encode_intra"
+    st = _stream() if stream is None else _c.c_void_p(stream.cuda_stream)
+    _rc(getattr(lib(), fname)(_c.byref(e), mb_width, mb_height, nframes, st), fname)
     out["recon"], out["recon_chroma"] = recon, recon_chroma if cf else None
     return out
 

@@ -14,6 +14,7 @@
 #include "x264hip_mc.h"
 #include "x264hip_deblock.h"
 #include "x264hip_mbenc.h"
+#include "x264hip_mbintra.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -1740,6 +1741,64 @@ extern "C" int x264hip_10_mb_encode_inter( const x264hip_mbenc_t *e, int mb_widt
                                            void *stream )
 {
     return mb_encode_inter_entry<10>( e, mb_width, mb_height, n_frames, stream );
+}
+
+// ------------------------------------------------------------ intra MB encode (x264hip_mbintra.h)
+// every argument error is X264HIP_EINVAL before any HIP call; of the pointers only e and
+// e->chroma_qp_table (host memory) are dereferenced.  The launches, one per macroblock
+// anti-diagonal, are launch_mb_encode_intra's loop.
+template <int BD>
+static int mb_encode_intra_entry( const x264hip_mbintra_t *e, int mb_width, int mb_height, int n_frames, void *stream )
+{
+    if( !e || mb_width < 0 || mb_height < 0 || n_frames < 0 )
+        return X264HIP_EINVAL;
+    const int cf = e->chroma_format;
+    if( cf < 0 || cf > 2 || !e->chroma_qp_table || !e->quant4_mf || !e->quant4_bias || !e->dequant4_mf || !e->fenc ||
+        !e->recon || !e->qp || !e->mb_flags || !e->pred_mode || !e->level || !e->chroma_dc || !e->nnz || !e->cbp ||
+        !e->nz || !e->flags_out || !e->luma_dc )
+        return X264HIP_EINVAL;
+    if( cf && ( !e->fenc_chroma || !e->recon_chroma || !e->chroma_pred_mode ) )
+        return X264HIP_EINVAL;
+    const int n8 = !e->quant8_mf + !e->quant8_bias + !e->dequant8_mf;
+    if( n8 != 0 && n8 != 3 )
+        return X264HIP_EINVAL;
+    constexpr int QP_MAX_SPEC = 51 + 6 * (BD - 8);
+    for( int q = 0; q <= QP_MAX_SPEC; q++ )
+        if( e->chroma_qp_table[q] > QP_MAX_SPEC - ( cf == 2 ? 3 : 0 ) )
+            return X264HIP_EINVAL;
+    const int64_t mbs = (int64_t)n_frames * mb_width * mb_height;
+    if( mbs > ( 1 << 28 ) )
+        return X264HIP_EINVAL;
+    // blocks are stored as whole dwords: outputs on 4-pixel boundaries (the mb_mc rule)
+    const uintptr_t px = sizeof( typename PT<BD>::pixel ), co = sizeof( typename PT<BD>::dctcoef );
+    bool bad = (uintptr_t)e->recon % (4 * px) || e->recon_stride % 4 || e->recon_frame_stride % 4;
+    if( cf )
+        bad |= (uintptr_t)e->recon_chroma % (4 * px) || e->recon_chroma_stride % 4 || e->recon_chroma_frame_stride % 4;
+    bad |= (uintptr_t)e->level % co || (uintptr_t)e->chroma_dc % co || (uintptr_t)e->luma_dc % co ||
+           (uintptr_t)e->cbp % 4 || (uintptr_t)e->nz % 4;
+    if( bad )
+    {
+        snprintf( t_err, sizeof(t_err), "x264hip_mb_encode_intra: misaligned reconstruction plane or output array" );
+        return X264HIP_EINVAL;
+    }
+    if( mbs == 0 )
+        return X264HIP_OK;
+    if( int rc = any_device() )
+        return rc;
+    return map_err( launch_mb_encode_intra<BD>( e, mb_width, mb_height, n_frames, (hipStream_t)stream ),
+                    "mb_encode_intra" );
+}
+
+extern "C" int x264hip_8_mb_encode_intra( const x264hip_mbintra_t *e, int mb_width, int mb_height, int n_frames,
+                                          void *stream )
+{
+    return mb_encode_intra_entry<8>( e, mb_width, mb_height, n_frames, stream );
+}
+
+extern "C" int x264hip_10_mb_encode_intra( const x264hip_mbintra_t *e, int mb_width, int mb_height, int n_frames,
+                                           void *stream )
+{
+    return mb_encode_intra_entry<10>( e, mb_width, mb_height, n_frames, stream );
 }
 
 // dequant4_mf / dequant8_mf of x264_cqm_init, reference common/set.c:31-39,

@@ -709,3 +709,10 @@ namespace x264hip {
 template <int BD>
 hipError_t launch_mb_encode_inter( const x264hip_mbenc_t *e, int mbw, int mbh, int n_frames, hipStream_t stream );
 } // namespace x264hip
+
+// the intra macroblock encode (mbintra.hip; include/x264hip_mbintra.h)
+struct x264hip_mbintra_t;
+namespace x264hip {
+template <int BD>
+hipError_t launch_mb_encode_intra( const x264hip_mbintra_t *e, int mbw, int mbh, int n_frames, hipStream_t stream );
+} // namespace x264hip

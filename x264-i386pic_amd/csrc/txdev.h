@@ -1,6 +1,6 @@
 // Device cores of the transform path, shared by dct.hip (forward transforms and quantisation),
-// idct.hip (dequantisation, inverse transforms, reconstruction) and mbenc.hip (the fused inter
-// macroblock encode): every block lives in one lane's registers.
+// idct.hip (dequantisation, inverse transforms, reconstruction), mbenc.hip and mbintra.hip (the fused
+// inter and intra macroblock encodes): every block lives in one lane's registers.
 //
 // Semantics (reference, all integer, bit-exact):
 //   sub4x4_dct                     common/dct.c:157-189 (int16 temps at 8 bit)
@@ -10,6 +10,8 @@
 //   add8x8_idct8                   common/dct.c:388-440
 //   dequant_4x4 / dequant_8x8      common/quant.c:106-146
 //   the 2x2 / 2x4 DC butterflies   common/dct.c:109-143, 207-270, common/quant.c:164-208
+//   dct4x4dc / idct4x4dc           common/dct.c:47-107
+//   dequant_4x4_dc                 common/quant.c:148-165
 //   optimize_chroma_2x2_dc/2x4_dc  common/quant.c:210-293
 //   decimate_score15/16/64         common/quant.c:318-352
 // Every dctcoef store of the reference (int16 at 8 bit) is reproduced with sto<BD>.
@@ -297,6 +299,41 @@ __device__ __forceinline__ void had2x4( const int (&d)[8], int (&v)[8] )
     const int b4 = a0 - a1, b5 = a2 - a3, b6 = a4 - a5, b7 = a6 - a7;
     v[0] = b0 + b1; v[1] = b2 + b3; v[2] = b0 - b1; v[3] = b2 - b3;
     v[4] = b4 - b5; v[5] = b6 - b7; v[6] = b4 + b5; v[7] = b6 + b7;
+}
+
+// ---------------------------------------------------------------- luma DC (I_16x16)
+// dct4x4dc (FWD: the halving second pass) and idct4x4dc, dct.c:47-107, in place; tmp and d are
+// stored as dctcoef
+template <int BD, bool FWD> __device__ __forceinline__ void had4x4dc( int (&d)[16] )
+{
+    int t[16];
+#pragma unroll
+    for( int i = 0; i < 4; i++ )
+    {
+        const int s01 = d[i * 4 + 0] + d[i * 4 + 1], d01 = d[i * 4 + 0] - d[i * 4 + 1];
+        const int s23 = d[i * 4 + 2] + d[i * 4 + 3], d23 = d[i * 4 + 2] - d[i * 4 + 3];
+        t[0 * 4 + i] = sto<BD>( s01 + s23 );
+        t[1 * 4 + i] = sto<BD>( s01 - s23 );
+        t[2 * 4 + i] = sto<BD>( d01 - d23 );
+        t[3 * 4 + i] = sto<BD>( d01 + d23 );
+    }
+    constexpr int R = FWD ? 1 : 0;
+#pragma unroll
+    for( int i = 0; i < 4; i++ )
+    {
+        const int s01 = t[i * 4 + 0] + t[i * 4 + 1], d01 = t[i * 4 + 0] - t[i * 4 + 1];
+        const int s23 = t[i * 4 + 2] + t[i * 4 + 3], d23 = t[i * 4 + 2] - t[i * 4 + 3];
+        d[i * 4 + 0] = sto<BD>( (s01 + s23 + R) >> R );
+        d[i * 4 + 1] = sto<BD>( (s01 - s23 + R) >> R );
+        d[i * 4 + 2] = sto<BD>( (d01 - d23 + R) >> R );
+        d[i * 4 + 3] = sto<BD>( (d01 + d23 + R) >> R );
+    }
+}
+
+// dequant_4x4_dc of one coefficient (quant.c:148-165): m = dequant_mf[qp % 6][0], qb = qp / 6 - 6
+__device__ __forceinline__ int dequant_dc_one( int v, int m, int qb )
+{
+    return qb >= 0 ? v * (m << qb) : (v * m + (1 << (-qb - 1))) >> (-qb);
 }
 
 // optimize_chroma_2x2_dc / 2x4_dc (quant.c:210-293): the dequantised, inverse-transformed DC
