@@ -59,7 +59,8 @@
  *              are copied unchanged.  The one array written for intra macroblocks too.
  *
  * Not included: 4:4:4 (it needs the chroma categories of dequant8_mf, which x264hip_cqm_dequant
- * does not produce, and the plane loop whose i_decimate_mb carries across planes); intra
+ * does not produce, and the plane loop whose i_decimate_mb carries across planes:
+ * x264hip_*_mb_encode_inter_444 of x264hip_mb444.h has both); intra
  * macroblocks; lossless, trellis, noise reduction; the P_SKIP / B_SKIP conversion of
  * macroblock.c:953-971 (it needs pskip_mv; the caller has cbp); zigzag_interleave_8x8_cavlc
  * (x264hip_*_zigzag_interleave_batch does it).

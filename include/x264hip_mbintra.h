@@ -60,7 +60,8 @@
  *   nz         int32 [mb] from nnz as the inter entry (4 bits for I_8x8, else 16);
  *   flags_out  uint8 [mb] = mb_flags[mb] & 3.
  *
- * Not included: I_PCM; 4:4:4; multiple slices and constrained_intra_pred; lossless, trellis,
+ * Not included: I_PCM; 4:4:4 (x264hip_*_mb_encode_intra_444 of x264hip_mb444.h has it); multiple
+ * slices and constrained_intra_pred; lossless, trellis,
  * noise reduction; the i_skip_intra reuse of the analysis' reconstruction; the mode decision.
  *
  * Contract: only pixels of [0, 16*mb_width) x [0, 16*mb_height) of recon and fenc and the matching

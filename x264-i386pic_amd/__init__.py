@@ -35,6 +35,7 @@ __all__ = [
     "deblock_strength", "deblock_frames", "chroma_qp_table", "Deblock", "DeblockStrength",
     "mb_encode_inter", "MbEnc", "MBENC_INTRA", "MBENC_T8x8", "MBENC_D16x16", "MBENC_SKIP", "MBENC_OUTPUTS",
     "mb_encode_intra", "MbIntra", "MBINTRA_I16x16", "MBINTRA_OUTPUTS",
+    "cqm_init444", "cqm_dequant444", "mb_encode_inter_444", "mb_encode_intra_444", "Mb444", "MB444_OUTPUTS",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -340,7 +341,8 @@ def cqm_dequant(scaling_lists, transform_8x8=True):
 
 # ----------------------------------------------------------------- declarations
 # Every function of include/x264hip.h, include/x264hip_mbtree.h, include/x264hip_mc.h,
-# include/x264hip_deblock.h, include/x264hip_mbenc.h and include/x264hip_mbintra.h, once:
+# include/x264hip_deblock.h, include/x264hip_mbenc.h, include/x264hip_mbintra.h and
+# include/x264hip_mb444.h, once:
 # "return:parameters", one letter each, in the struct module's spelling where it has one.
 # tests/test_abi.py checks the first two tables against x264hip.h's prototypes,
 # tests/test_cpu_mbtree.py the third against x264hip_mbtree.h's, tests/test_cpu_mc.py the fourth
@@ -472,6 +474,16 @@ _MBENC = {
 _MBINTRA = {
     "mb_encode_intra": "i:PiiiP",
 }
+# include/x264hip_mb444.h: x264hip_8_<name> and x264hip_10_<name>, then x264hip_<name>
+# (tests/test_cpu_mb444.py checks both against the header's prototypes)
+_MB444 = {
+    "cqm_init444": "i:PiiPPPP",
+    "mb_encode_inter_444": "i:PiiiP",
+    "mb_encode_intra_444": "i:PiiiP",
+}
+_MB444_PLAIN = {
+    "cqm_dequant444": "v:PPP",
+}
 
 
 def _declare(L):
@@ -500,6 +512,11 @@ def _declare(L):
     for name, sig in _MBINTRA.items():
         for bd in (8, 10):
             declare(getattr(L, f"x264hip_{bd}_{name}"), sig)
+    for name, sig in _MB444.items():
+        for bd in (8, 10):
+            declare(getattr(L, f"x264hip_{bd}_{name}"), sig)
+    for name, sig in _MB444_PLAIN.items():
+        declare(getattr(L, f"x264hip_{name}"), sig)
 
 
 # ----------------------------------------------------------------- CQM
@@ -1556,6 +1573,147 @@ def mb_encode_intra(fenc, recon, mb_width, mb_height, nframes, qp, mb_flags, pre
     _rc(getattr(lib(), fname)(_c.byref(e), mb_width, mb_height, nframes, st), fname)
     out["recon"], out["recon_chroma"] = recon, recon_chroma if cf else None
     return out
+
+
+# ----------------------------------------------------------------- the two at 4:4:4 (include/x264hip_mb444.h)
+def cqm_init444(bitdepth, scaling_lists, deadzone_inter=21, deadzone_intra=11):
+    """cqm_init with all four 8x8 categories written (x264_cqm_init with num_8x8_lists = 4, reference
+    common/set.c:87,154-159,186-205): quant8_mf / quant8_bias [4][QP+1][64] hold CQM_8IY, CQM_8PY,
+    CQM_8IC, CQM_8PC from scaling_lists[4..7].  Returns (quant4_mf, quant4_bias, quant8_mf, quant8_bias)."""
+    _check_bd(bitdepth)
+    qp1 = 52 + 6 * (bitdepth - 8)
+    ut = np.uint16 if bitdepth == 8 else np.uint32
+    q4m, q4b = np.zeros((4, qp1, 16), ut), np.zeros((4, qp1, 16), ut)
+    q8m, q8b = np.zeros((4, qp1, 64), ut), np.zeros((4, qp1, 64), ut)
+    lists = [np.ascontiguousarray(np.asarray(s, np.uint8)) for s in scaling_lists]
+    ptrs = (_P * 8)(*[x.ctypes.data for x in lists])
+    getattr(lib(), f"x264hip_{bitdepth}_cqm_init444")(
+        ptrs, deadzone_inter, deadzone_intra, q4m.ctypes.data, q4b.ctypes.data, q8m.ctypes.data, q8b.ctypes.data)
+    return q4m, q4b, q8m, q8b
+
+
+def cqm_dequant444(scaling_lists):
+    """dequant4_mf [4][6][16], dequant8_mf [4][6][64] (int32): cqm_dequant with the 8x8 chroma categories."""
+    lists = [np.ascontiguousarray(np.asarray(x, np.uint8)) for x in scaling_lists]
+    ptrs = (_P * 8)(*[x.ctypes.data for x in lists])
+    dq4 = np.zeros((4, 6, 16), np.int32)
+    dq8 = np.zeros((4, 6, 64), np.int32)
+    lib().x264hip_cqm_dequant444(ptrs, dq4.ctypes.data, dq8.ctypes.data)
+    return dq4, dq8
+
+
+class Mb444(_c.Structure):
+    """x264hip_mb444_t"""
+    _fields_ = [("b_dct_decimate", _c.c_int32), ("chroma_qp_table", _P),
+                ("quant4_mf", _P), ("quant4_bias", _P), ("quant8_mf", _P), ("quant8_bias", _P),
+                ("dequant4_mf", _P), ("dequant8_mf", _P),
+                ("fenc", _P * 3), ("fenc_stride", _IP), ("fenc_frame_stride", _IP),
+                ("fenc_chroma_stride", _IP), ("fenc_chroma_frame_stride", _IP),
+                ("pred", _P * 3), ("pred_stride", _IP), ("pred_frame_stride", _IP),
+                ("pred_chroma_stride", _IP), ("pred_chroma_frame_stride", _IP),
+                ("recon", _P * 3), ("recon_stride", _IP), ("recon_frame_stride", _IP),
+                ("recon_chroma_stride", _IP), ("recon_chroma_frame_stride", _IP),
+                ("qp", _P), ("mb_flags", _P), ("pred_mode", _P),
+                ("level", _P), ("nnz", _P), ("cbp", _P), ("nz", _P), ("flags_out", _P), ("luma_dc", _P)]
+
+
+MB444_OUTPUTS = ("level", "nnz", "cbp", "nz", "flags_out", "luma_dc")
+
+
+def _mb444(who, intra, fenc, pred, recon, mb_width, mb_height, nframes, qp, mb_flags, pred_mode, quant4, dequant4_mf,
+           quant8, dequant8_mf, b_dct_decimate, qp_table, chroma_qp_index_offset, outs, stream):
+    """the struct and the call of both 4:4:4 entries; a picture is (luma, chroma) with luma =
+    (tensor, origin, stride, frame_stride) and chroma = ([U, V], origin, stride, frame_stride)"""
+    import torch
+    for name, pic in (("fenc", fenc), ("pred", pred), ("recon", recon)):
+        if pic is not None and (len(pic) != 2 or len(pic[0]) != 4 or len(pic[1]) != 4 or len(pic[1][0]) != 2):
+            raise ValueError(f"{who}: {name} is (luma, chroma) = ((Y, origin, stride, frame_stride), "
+                             "([U, V], origin, stride, frame_stride))")
+    bd = _pix_bd(recon[0][0])
+    if (quant8 is None) != (dequant8_mf is None):
+        raise ValueError(f"{who}: quant8 and dequant8_mf come together")
+    if mb_width < 0 or mb_height < 0 or nframes < 0:
+        raise ValueError(f"{who}: negative size")
+    table = chroma_qp_table(bd, chroma_qp_index_offset) if qp_table is None else \
+        np.ascontiguousarray(np.asarray(qp_table, np.uint8))
+    if table.size < 52 + 6 * (bd - 8):
+        raise ValueError(f"{who}: the chroma qp table needs QP_MAX_SPEC + 1 entries")
+    nmb = nframes * mb_width * mb_height
+    if qp.numel() < nmb or mb_flags.numel() < nmb:
+        raise ValueError(f"{who}: qp and mb_flags need one element per macroblock")
+    if intra and (pred_mode.dtype != torch.int8 or pred_mode.numel() < 16 * nmb or not pred_mode.is_contiguous()):
+        raise ValueError(f"{who}: pred_mode must be a contiguous int8 tensor of 16 modes per macroblock")
+    cdt = torch.int16 if bd == 8 else torch.int32
+    shapes = {"level": ((nmb, 48, 16), cdt), "nnz": ((nmb, 48), torch.uint8), "cbp": ((nmb,), torch.int32),
+              "nz": ((nmb,), torch.int32), "flags_out": ((nmb,), torch.uint8), "luma_dc": ((nmb, 3, 16), cdt)}
+    out = {k: v for k, v in (outs or {}).items() if k in shapes}
+    for name, (shape, dt) in shapes.items():
+        if name not in out:
+            out[name] = torch.zeros(shape, dtype=dt, device=recon[0][0].device)
+        elif out[name].dtype != dt or out[name].numel() < int(np.prod(shape)) or not out[name].is_contiguous():
+            raise ValueError(f"{who}: {name} must be a contiguous {dt} tensor of {shape}")
+    e = Mb444()
+    e.b_dct_decimate = int(bool(b_dct_decimate))
+    e.chroma_qp_table = table.ctypes.data
+    e.quant4_mf, e.quant4_bias, e.dequant4_mf = _ptr(quant4[0]).value, _ptr(quant4[1]).value, _ptr(dequant4_mf).value
+    if quant8 is not None:
+        e.quant8_mf, e.quant8_bias, e.dequant8_mf = _ptr(quant8[0]).value, _ptr(quant8[1]).value, _ptr(dequant8_mf).value
+    for name, pic in (("fenc", fenc), ("pred", pred), ("recon", recon)):
+        if pic is None:
+            continue
+        (y, origin, stride, fstride), (uv, c_origin, c_stride, c_fstride) = pic
+        if any(_pix_bd(t) != bd for t in (y, *uv)):
+            raise TypeError(f"{who}: the planes disagree on the bit depth")
+        ptrs = getattr(e, name)
+        ptrs[0] = _ptr(y, origin).value
+        ptrs[1], ptrs[2] = _ptr(uv[0], c_origin).value, _ptr(uv[1], c_origin).value
+        setattr(e, name + "_stride", stride)
+        setattr(e, name + "_frame_stride", fstride)
+        setattr(e, name + "_chroma_stride", c_stride)
+        setattr(e, name + "_chroma_frame_stride", c_fstride)
+    # (torch gives an empty tensor a NULL pointer; with no macroblock the arrays are not read)
+    dummy = _c.addressof(e)
+    e.qp = _ptr(qp).value or dummy
+    e.mb_flags = _ptr(mb_flags).value or dummy
+    if intra:
+        e.pred_mode = _ptr(pred_mode).value or dummy
+    for name in MB444_OUTPUTS:
+        setattr(e, name, _ptr(out[name]).value or dummy)
+    fname = f"x264hip_{bd}_mb_encode_{'intra' if intra else 'inter'}_444"
+    st = _stream() if stream is None else _c.c_void_p(stream.cuda_stream)
+    _rc(getattr(lib(), fname)(_c.byref(e), mb_width, mb_height, nframes, st), fname)
+    out["recon"] = recon
+    return out
+
+
+def mb_encode_inter_444(fenc, pred, mb_width, mb_height, nframes, qp, mb_flags, quant4, dequant4_mf, quant8=None,
+                        dequant8_mf=None, recon=None, b_dct_decimate=True, qp_table=None, chroma_qp_index_offset=0,
+                        outs=None, stream=None):
+    """x264_macroblock_encode of every inter macroblock of nframes 4:4:4 frames
+    (x264hip_*_mb_encode_inter_444, include/x264hip_mb444.h).  A picture is (luma, chroma): luma =
+    (Y tensor, origin, stride, frame_stride) as mb_encode_inter's planes, chroma = ([U, V], origin,
+    stride, frame_stride) with the two tensors mb_mc returns at chroma_format 3.  pred is what
+    mb_mc wrote; recon None reconstructs in place.  quant4 / quant8: the device copies of
+    cqm_init444's tables, dequant4_mf / dequant8_mf of cqm_dequant444's ([4][6][64]).  qp, mb_flags,
+    qp_table and outs as mb_encode_inter, stream as mb_encode_intra; outs may name any of
+    MB444_OUTPUTS (luma_dc is not written by this call).  Returns a dict: recon and MB444_OUTPUTS."""
+    return _mb444("mb_encode_inter_444", False, fenc, pred, pred if recon is None else recon, mb_width, mb_height,
+                  nframes, qp, mb_flags, None, quant4, dequant4_mf, quant8, dequant8_mf, b_dct_decimate, qp_table,
+                  chroma_qp_index_offset, outs, stream)
+
+
+def mb_encode_intra_444(fenc, recon, mb_width, mb_height, nframes, qp, mb_flags, pred_mode, quant4, dequant4_mf,
+                        quant8=None, dequant8_mf=None, b_dct_decimate=True, qp_table=None, chroma_qp_index_offset=0,
+                        outs=None, stream=None):
+    """x264_macroblock_encode of every intra macroblock of nframes 4:4:4 frames
+    (x264hip_*_mb_encode_intra_444, include/x264hip_mb444.h), after mb_encode_inter_444 on the same
+    recon planes and before deblocking: U and V take the luma path with the luma modes pred_mode
+    int8 [mbs][16] (there is no chroma_pred_mode).  Pictures, tables and the rest as
+    mb_encode_inter_444; outs: for instance the dict that call returned.  Returns a dict: recon and
+    MB444_OUTPUTS (luma_dc [mbs][3][16])."""
+    return _mb444("mb_encode_intra_444", True, fenc, None, recon, mb_width, mb_height, nframes, qp, mb_flags, pred_mode,
+                  quant4, dequant4_mf, quant8, dequant8_mf, b_dct_decimate, qp_table, chroma_qp_index_offset, outs,
+                  stream)
 
 
 def plane_stride(width, pad=PAD):

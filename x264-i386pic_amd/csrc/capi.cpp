@@ -15,6 +15,7 @@
 #include "x264hip_deblock.h"
 #include "x264hip_mbenc.h"
 #include "x264hip_mbintra.h"
+#include "x264hip_mb444.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -1384,8 +1385,10 @@ static const uint16_t k_quant8_scale[6][6] = {
 static inline int cqm_div( int n, int d ) { return (n + (d >> 1)) / d; }
 static inline int cqm_shift( int x, int s ) { return s <= 0 ? x << -s : (x + (1 << (s - 1))) >> s; }
 
+// n8: the 8x8 lists written, set.c's num_8x8_lists (2: CQM_8IY, CQM_8PY; 4 at 4:4:4: CQM_8IC and
+// CQM_8PC too, x264hip_mb444.h) or 0
 template <int BD>
-static int cqm_init( const uint8_t *const sl[8], int dz_inter, int dz_intra, int b8, typename PT<BD>::udctcoef *q4m,
+static int cqm_init( const uint8_t *const sl[8], int dz_inter, int dz_intra, int n8, typename PT<BD>::udctcoef *q4m,
                      typename PT<BD>::udctcoef *q4b, typename PT<BD>::udctcoef *q8m, typename PT<BD>::udctcoef *q8b )
 {
     const int qmax = 51 + 6 * (BD - 8);
@@ -1405,20 +1408,19 @@ static int cqm_init( const uint8_t *const sl[8], int dz_inter, int dz_intra, int
                     q4b[o] = a < b ? a : b;
                 }
             }
-        if( b8 )
-            for( int l = 0; l < 2; l++ )
-                for( int i = 0; i < 64; i++ )
+        for( int l = 0; l < n8; l++ )
+            for( int i = 0; i < 64; i++ )
+            {
+                int base = cqm_div( k_quant8_scale[q % 6][k_quant8_scan[((i >> 1) & 12) | (i & 3)]] * 16, sl[4 + l][i] );
+                int j = cqm_shift( base, q / 6 );
+                size_t o = ((size_t)l * (qmax + 1) + q) * 64 + i;
+                q8m[o] = (uint16_t)j;
+                if( j )
                 {
-                    int base = cqm_div( k_quant8_scale[q % 6][k_quant8_scan[((i >> 1) & 12) | (i & 3)]] * 16, sl[4 + l][i] );
-                    int j = cqm_shift( base, q / 6 );
-                    size_t o = ((size_t)l * (qmax + 1) + q) * 64 + i;
-                    q8m[o] = (uint16_t)j;
-                    if( j )
-                    {
-                        int a = cqm_div( dz[l] << 10, j ), b = (1 << 15) / j;
-                        q8b[o] = a < b ? a : b;
-                    }
+                    int a = cqm_div( dz[l] << 10, j ), b = (1 << 15) / j;
+                    q8b[o] = a < b ? a : b;
                 }
+            }
     }
     return qmax;
 }
@@ -1810,17 +1812,116 @@ static const uint8_t k_dequant8_scale[6][6] = {
     { 28, 25, 45, 26, 35, 33 }, { 32, 28, 51, 30, 40, 38 }, { 36, 32, 58, 34, 46, 43 } };
 static const uint8_t k_quant8_scan16[16] = { 0, 3, 4, 3, 3, 1, 5, 1, 4, 5, 2, 5, 3, 1, 5, 1 };
 
-extern "C" void x264hip_cqm_dequant( const uint8_t *const sl[8], int b8, int32_t *dq4, int32_t *dq8 )
+// n8 as cqm_init's
+static void cqm_dequant( const uint8_t *const sl[8], int n8, int32_t *dq4, int32_t *dq8 )
 {
     for( int q = 0; q < 6; q++ )
     {
         for( int l = 0; l < 4; l++ )
             for( int i = 0; i < 16; i++ )
                 dq4[(l * 6 + q) * 16 + i] = k_dequant4_scale[q][(i & 1) + ((i >> 2) & 1)] * sl[l][i];
-        if( b8 )
-            for( int l = 0; l < 2; l++ )
-                for( int i = 0; i < 64; i++ )
-                    dq8[(l * 6 + q) * 64 + i] =
-                        k_dequant8_scale[q][k_quant8_scan16[((i >> 1) & 12) | (i & 3)]] * sl[4 + l][i];
+        for( int l = 0; l < n8; l++ )
+            for( int i = 0; i < 64; i++ )
+                dq8[(l * 6 + q) * 64 + i] =
+                    k_dequant8_scale[q][k_quant8_scan16[((i >> 1) & 12) | (i & 3)]] * sl[4 + l][i];
     }
+}
+
+extern "C" void x264hip_cqm_dequant( const uint8_t *const sl[8], int b8, int32_t *dq4, int32_t *dq8 )
+{
+    cqm_dequant( sl, b8 ? 2 : 0, dq4, dq8 );
+}
+
+// ------------------------------------------------------------ 4:4:4 (x264hip_mb444.h)
+extern "C" void x264hip_cqm_dequant444( const uint8_t *const sl[8], int32_t *dq4, int32_t *dq8 )
+{
+    cqm_dequant( sl, 4, dq4, dq8 );
+}
+
+extern "C" int x264hip_8_cqm_init444( const uint8_t *const sl[8], int dz_inter, int dz_intra, uint16_t *q4m,
+                                      uint16_t *q4b, uint16_t *q8m, uint16_t *q8b )
+{
+    return cqm_init<8>( sl, dz_inter, dz_intra, 4, q4m, q4b, q8m, q8b );
+}
+
+extern "C" int x264hip_10_cqm_init444( const uint8_t *const sl[8], int dz_inter, int dz_intra, uint32_t *q4m,
+                                       uint32_t *q4b, uint32_t *q8m, uint32_t *q8b )
+{
+    return cqm_init<10>( sl, dz_inter, dz_intra, 4, q4m, q4b, q8m, q8b );
+}
+
+// every argument error is X264HIP_EINVAL before any HIP call; of the pointers only e and
+// e->chroma_qp_table (host memory) are dereferenced.  The two entries differ in the fields they
+// need (pred; pred_mode and luma_dc) and in the launcher.
+template <int BD>
+static int mb_encode_444_entry( const x264hip_mb444_t *e, int mb_width, int mb_height, int n_frames, void *stream,
+                                bool intra )
+{
+    if( !e || mb_width < 0 || mb_height < 0 || n_frames < 0 )
+        return X264HIP_EINVAL;
+    if( !e->chroma_qp_table || !e->quant4_mf || !e->quant4_bias || !e->dequant4_mf || !e->qp || !e->mb_flags ||
+        !e->level || !e->nnz || !e->cbp || !e->nz || !e->flags_out )
+        return X264HIP_EINVAL;
+    for( int p = 0; p < 3; p++ )
+        if( !e->fenc[p] || !e->recon[p] || ( !intra && !e->pred[p] ) )
+            return X264HIP_EINVAL;
+    if( intra && ( !e->pred_mode || !e->luma_dc ) )
+        return X264HIP_EINVAL;
+    const int n8 = !e->quant8_mf + !e->quant8_bias + !e->dequant8_mf;
+    if( n8 != 0 && n8 != 3 )
+        return X264HIP_EINVAL;
+    constexpr int QP_MAX_SPEC = 51 + 6 * (BD - 8);
+    for( int q = 0; q <= QP_MAX_SPEC; q++ )
+        if( e->chroma_qp_table[q] > QP_MAX_SPEC )
+            return X264HIP_EINVAL;
+    const int64_t mbs = (int64_t)n_frames * mb_width * mb_height;
+    if( mbs > ( 1 << 28 ) )
+        return X264HIP_EINVAL;
+    // blocks are stored as whole dwords: outputs on 4-pixel boundaries (the mb_mc rule)
+    const uintptr_t px = sizeof( typename PT<BD>::pixel ), co = sizeof( typename PT<BD>::dctcoef );
+    bool bad = e->recon_stride % 4 || e->recon_frame_stride % 4 || e->recon_chroma_stride % 4 ||
+               e->recon_chroma_frame_stride % 4;
+    for( int p = 0; p < 3; p++ )
+        bad |= (uintptr_t)e->recon[p] % (4 * px) != 0;
+    bad |= (uintptr_t)e->level % co || (uintptr_t)e->cbp % 4 || (uintptr_t)e->nz % 4 ||
+           ( intra && (uintptr_t)e->luma_dc % co );
+    if( bad )
+    {
+        snprintf( t_err, sizeof(t_err), "x264hip_mb_encode_%s_444: misaligned reconstruction plane or output array",
+                  intra ? "intra" : "inter" );
+        return X264HIP_EINVAL;
+    }
+    if( mbs == 0 )
+        return X264HIP_OK;
+    if( int rc = any_device() )
+        return rc;
+    if( intra )
+        return map_err( launch_mb_encode_intra_444<BD>( e, mb_width, mb_height, n_frames, (hipStream_t)stream ),
+                        "mb_encode_intra_444" );
+    return map_err( launch_mb_encode_inter_444<BD>( e, mb_width, mb_height, n_frames, (hipStream_t)stream ),
+                    "mb_encode_inter_444" );
+}
+
+extern "C" int x264hip_8_mb_encode_inter_444( const x264hip_mb444_t *e, int mb_width, int mb_height, int n_frames,
+                                              void *stream )
+{
+    return mb_encode_444_entry<8>( e, mb_width, mb_height, n_frames, stream, false );
+}
+
+extern "C" int x264hip_10_mb_encode_inter_444( const x264hip_mb444_t *e, int mb_width, int mb_height, int n_frames,
+                                               void *stream )
+{
+    return mb_encode_444_entry<10>( e, mb_width, mb_height, n_frames, stream, false );
+}
+
+extern "C" int x264hip_8_mb_encode_intra_444( const x264hip_mb444_t *e, int mb_width, int mb_height, int n_frames,
+                                              void *stream )
+{
+    return mb_encode_444_entry<8>( e, mb_width, mb_height, n_frames, stream, true );
+}
+
+extern "C" int x264hip_10_mb_encode_intra_444( const x264hip_mb444_t *e, int mb_width, int mb_height, int n_frames,
+                                               void *stream )
+{
+    return mb_encode_444_entry<10>( e, mb_width, mb_height, n_frames, stream, true );
 }

@@ -98,7 +98,7 @@ extern "C" int BD_NAME( cqm_init )( const uint8_t *const sl[8], int dz_inter, in
                                     PT<BD>::udctcoef *q4m, PT<BD>::udctcoef *q4b, PT<BD>::udctcoef *q8m,
                                     PT<BD>::udctcoef *q8b )
 {
-    return cqm_init<BD>( sl, dz_inter, dz_intra, b8, q4m, q4b, q8m, q8b );
+    return cqm_init<BD>( sl, dz_inter, dz_intra, b8 ? 2 : 0, q4m, q4b, q8m, q8b );
 }
 
 extern "C" int BD_NAME( pixel_cmp_batch )( int op, int i_pixel, const PT<BD>::pixel *fenc, intptr_t fs,

@@ -2,7 +2,8 @@
 // macroblock_encode_internal (reference encoder/macroblock.c:618-972) and
 // mb_encode_chroma_internal (:259-490) for inter macroblocks over the transform cores of txdev.h.
 //
-// Mapping: 16 lanes per macroblock, four macroblocks per wave.  Luma, transform 4: lane l owns the
+// Mapping: 16 lanes per macroblock, four macroblocks per wave.  Luma (mbencdev.h's plane, shared
+// with mb444.hip), transform 4: lane l owns the
 // 4x4 block l of h->dct.luma4x4's order; transform 8: lanes 0..3 own the 8x8 blocks.  Chroma: lane
 // c < 4 (4:2:0) or < 8 (4:2:2) owns the 4x4 position c of BOTH channels, the 8 interleaved samples
 // of each of its rows, so that pixels move as whole dwords.  What the reference decides per 8x8,
@@ -91,149 +92,34 @@ __global__ __launch_bounds__( 256 ) void mb_encode_inter_kernel( const MbEncPara
     dctcoef *lvl = a.level + (int64_t)mb * (48 * 16);
 
     // ---------------------------------------------------------------- luma
+    // one plane (mbencdev.h): i_decimate_mb at the test after it is the plane's own sum
+    PlaneCtx<BD> k;
+    k.fenc = a.fenc + (intptr_t)f * a.ffs + (intptr_t)(16 * mby) * a.fs + 16 * mbx;
+    k.pred = a.pred + (intptr_t)f * a.pfs + (intptr_t)(16 * mby) * a.ps + 16 * mbx;
+    k.recon = a.recon + (intptr_t)f * a.rfs + (intptr_t)(16 * mby) * a.rs + 16 * mbx;
+    k.fs = a.fs; k.ps = a.ps; k.rs = a.rs;
+    k.mf4 = a.q4mf + (CQM_4PY * QP1 + qp) * 16; k.bias4 = a.q4b + (CQM_4PY * QP1 + qp) * 16;
+    k.mf8 = a.q8mf + (CQM_8PY * QP1 + qp) * 64; k.bias8 = a.q8b + (CQM_8PY * QP1 + qp) * 64;
+    k.dq4 = a.dq4 + CQM_4PY * 6 * 16; k.dq8 = a.dq8 + CQM_8PY * 6 * 64;
+    k.qp = qp; k.lvl = lvl; k.al = al;
     int lmask = 0;                             // non_zero_count of the 16 luma blocks, bit = block index
     int k4 = 0;                                // transform 8: the kept 8x8 blocks
     if( !t8 )
     {
-        const int i8 = l >> 2, i4 = l & 3;
-        const int x = (i8 & 1) * 8 + (i4 & 1) * 4, y = (i8 >> 1) * 8 + (i4 >> 1) * 4;
-        const pixel *fp = a.fenc + (intptr_t)f * a.ffs + (intptr_t)(16 * mby + y) * a.fs + 16 * mbx + x;
-        const pixel *pp = a.pred + (intptr_t)f * a.pfs + (intptr_t)(16 * mby + y) * a.ps + 16 * mbx + x;
-        pixel *rp = a.recon + (intptr_t)f * a.rfs + (intptr_t)(16 * mby + y) * a.rs + 16 * mbx + x;
-        int c[16];
-        zero( c );
-        int nzb = 0, score = 0;
-        if( !skip )
-        {
-            int d[4][4];
-            load_diff<BD, 4>( d, fp, a.fs, pp, a.ps );
-            dct4x4_core<BD>( d, c );
-            const typename PT<BD>::udctcoef *mf = a.q4mf + (CQM_4PY * QP1 + qp) * 16, *bias = a.q4b + (CQM_4PY * QP1 + qp) * 16;
-            int acc = 0;
-#pragma unroll
-            for( int k = 0; k < 16; k++ )
-            {
-                c[k] = sto<BD>( quant_one( c[k], mf[k], bias[k] ) );
-                acc |= c[k];
-            }
-            nzb = acc != 0;
-            if( a.dec && nzb )
-                score = decimate_score<16, 0>( [&]( int i ) { return c[ZZF<4>::x( i ) * 4 + ZZF<4>::y( i )]; } );
-        }
-        // the 8x8's decision (macroblock.c:862-905), taken by each of its four lanes
-        int i_decimate_8x8 = a.dec ? 0 : 6, nnz8x8 = 0;
-#pragma unroll
-        for( int k = 0; k < 4; k++ )
-        {
-            const int nzk = mb_lane( nzb, (l & 12) + k ), sk = mb_lane( score, (l & 12) + k );
-            if( nzk )
-            {
-                nnz8x8 = 1;
-                if( i_decimate_8x8 < 6 )
-                    i_decimate_8x8 += sk;
-            }
-        }
-        const int contrib = nnz8x8 ? i_decimate_8x8 : 0;
-        int i_decimate_mb = 0;
-#pragma unroll
-        for( int k = 0; k < 4; k++ )
-            i_decimate_mb += mb_lane( contrib, 4 * k );
-        const bool keep = nnz8x8 && i_decimate_8x8 >= 4 && i_decimate_mb >= 6;
-        const bool nn = keep && nzb;
-        int lev[16], res[4][4];
-        zero( lev );
-#pragma unroll
-        for( int yy = 0; yy < 4; yy++ )
-#pragma unroll
-            for( int xx = 0; xx < 4; xx++ )
-                res[yy][xx] = 0;
-        if( nn )
-        {
-#pragma unroll
-            for( int i = 0; i < 16; i++ )
-                lev[i] = c[ZZF<4>::x( i ) * 4 + ZZF<4>::y( i )];
-            const int32_t *m = a.dq4 + (CQM_4PY * 6 + qp % 6) * 16;
-            const int qb = qp / 6 - 4;
-#pragma unroll
-            for( int k = 0; k < 16; k++ )
-                c[k] = sto<BD>( dequant_one( c[k], m[k], qb ) );
-            idct4_residual<BD>( c, res );
-        }
-        put_coefs<BD, 16>( lvl + l * 16, lev, al );
-        add_block<BD, 4>( pp, a.ps, rp, a.rs, res );
+        Inter4 s;
+        inter_luma4_scores<BD>( k, l, a.dec, skip, s );
+        const bool nn = inter_luma4_finish<BD>( k, l, s, s.plane_score );
         lmask = (int)((__ballot( nn ) >> (16 * slot)) & 0xffff);
     }
     else
     {
-        const int x = (l & 1) * 8, y = ((l >> 1) & 1) * 8;
-        const pixel *fp = a.fenc + (intptr_t)f * a.ffs + (intptr_t)(16 * mby + y) * a.fs + 16 * mbx + x;
-        const pixel *pp = a.pred + (intptr_t)f * a.pfs + (intptr_t)(16 * mby + y) * a.ps + 16 * mbx + x;
-        pixel *rp = a.recon + (intptr_t)f * a.rfs + (intptr_t)(16 * mby + y) * a.rs + 16 * mbx + x;
-        int c[64];
-        zero( c );
-        int nzb = 0, score = 0;
-        if( l < 4 && !skip )
-        {
-            int d[8][8];
-            load_diff<BD, 8>( d, fp, a.fs, pp, a.ps );
-            dct8x8_core<BD>( d, c );
-            const typename PT<BD>::udctcoef *mf = a.q8mf + (CQM_8PY * QP1 + qp) * 64, *bias = a.q8b + (CQM_8PY * QP1 + qp) * 64;
-            int acc = 0;
+        Inter8 s;
+        inter_luma8_scores<BD>( k, l, a.dec, skip, s );
+        const bool keep = inter_luma8_finish<BD>( k, l, a.dec, s, s.plane_score );
+        k4 = (int)((__ballot( keep ) >> (16 * slot)) & 0xf);
 #pragma unroll
-            for( int k = 0; k < 64; k++ )
-            {
-                c[k] = sto<BD>( quant_one( c[k], mf[k], bias[k] ) );
-                acc |= c[k];
-            }
-            nzb = acc != 0;
-            if( a.dec && nzb )
-                score = decimate_score<64, 0>( [&]( int i ) { return c[ZZF<8>::x( i ) * 8 + ZZF<8>::y( i )]; } );
-        }
-        // macroblock.c:813-842
-        int i_decimate_mb = 0;
-#pragma unroll
-        for( int k = 0; k < 4; k++ )
-        {
-            const int nzk = mb_lane( nzb, k ), sk = mb_lane( score, k );
-            if( a.dec && nzk )
-                i_decimate_mb += sk;
-        }
-        const bool keep = nzb && (!a.dec || (score >= 4 && i_decimate_mb >= 6));
-        if( l < 4 )
-        {
-            int lev[64];
-            zero( lev );
-            if( keep )
-            {
-#pragma unroll
-                for( int i = 0; i < 64; i++ )
-                    lev[i] = c[ZZF<8>::x( i ) * 8 + ZZF<8>::y( i )];
-            }
-            put_coefs<BD, 64>( lvl + l * 64, lev, al );
-            int res[8][8];
-            if( keep )
-            {
-                const int32_t *m = a.dq8 + (CQM_8PY * 6 + qp % 6) * 64;
-                const int qb = qp / 6 - 6;
-#pragma unroll
-                for( int k = 0; k < 64; k++ )
-                    c[k] = sto<BD>( dequant_one( c[k], m[k], qb ) );
-                idct8_residual<BD>( c, res );
-            }
-            else
-            {
-#pragma unroll
-                for( int yy = 0; yy < 8; yy++ )
-#pragma unroll
-                    for( int xx = 0; xx < 8; xx++ )
-                        res[yy][xx] = 0;
-            }
-            add_block<BD, 8>( pp, a.ps, rp, a.rs, res );
-        }
-        k4 = (int)((__ballot( keep && l < 4 ) >> (16 * slot)) & 0xf);
-#pragma unroll
-        for( int k = 0; k < 4; k++ )
-            lmask |= ((k4 >> k) & 1) * (0xf << (4 * k));
+        for( int j = 0; j < 4; j++ )
+            lmask |= ((k4 >> j) & 1) * (0xf << (4 * j));
     }
     int cbp_luma = k4;
     if( !t8 )

@@ -1,7 +1,8 @@
-// Device helpers shared by the macroblock encodes, mbenc.hip (inter) and mbintra.hip (intra): the
-// 16-lanes-per-macroblock cross-lane reads, the coefficient stores, the static inlines of
-// encoder/macroblock.c:35-96 with their 2x4 counterparts, and one channel of
-// mb_encode_chroma_internal (reference encoder/macroblock.c:259-490) over the cores of txdev.h.
+// Device helpers shared by the macroblock encodes, mbenc.hip (inter), mbintra.hip (intra) and
+// mb444.hip (both at 4:4:4): the 16-lanes-per-macroblock cross-lane reads, the coefficient stores,
+// the static inlines of encoder/macroblock.c:35-96 with their 2x4 counterparts, one channel of
+// mb_encode_chroma_internal (reference encoder/macroblock.c:259-490) and one luma-coded plane of
+// an inter macroblock (:801-921) over the cores of txdev.h.
 #pragma once
 #include "txdev.h"
 
@@ -290,6 +291,190 @@ __device__ __forceinline__ void chroma_channel( const ChromaTabs<BD> &a, bool de
     }
     if( mine )
         idct4_residual<BD>( c, o.res );
+}
+
+// ---------------------------------------------------------------- one luma-coded plane
+// One plane of one macroblock as its 16 lanes see it: the luma plane of mbenc.hip / mbintra.hip,
+// or Y, U or V of a 4:4:4 macroblock (mb444.hip), each with its own quant category and qp.
+template <int BD> struct PlaneCtx
+{
+    using pixel = typename PT<BD>::pixel;
+    const pixel *fenc, *pred;                  // pixel (0,0) of the macroblock; pred: inter only
+    pixel *recon;
+    intptr_t fs, ps, rs;
+    const typename PT<BD>::udctcoef *mf4, *bias4, *mf8, *bias8;   // the category's rows at qp
+    const int32_t *dq4, *dq8;                  // the category's dequant4_mf [6][16] / dequant8_mf [6][64]
+    int qp;
+    typename PT<BD>::dctcoef *lvl;             // level of the plane's block 0
+    bool al;                                   // lvl is 16-byte aligned
+};
+
+// Inter, transform 4 (macroblock.c:848-919).  The first half runs up to the plane's own sum of
+// i_decimate_8x8 (what it adds to i_decimate_mb); the caller forms i_decimate_mb as the test
+// after this plane sees it (:907), and the second half takes the decisions and reconstructs.
+// Lane l owns block l of h->dct.luma4x4's order; uniform over the plane's lanes except l.
+struct Inter4
+{
+    int c[16];
+    int nzb, i_decimate_8x8, nnz8x8, plane_score;
+};
+
+template <int BD>
+__device__ __forceinline__ void inter_luma4_scores( const PlaneCtx<BD> &k, int l, bool dec, bool skip, Inter4 &s )
+{
+    const int i8 = l >> 2, i4 = l & 3;
+    const int x = (i8 & 1) * 8 + (i4 & 1) * 4, y = (i8 >> 1) * 8 + (i4 >> 1) * 4;
+    zero( s.c );
+    int score = 0;
+    s.nzb = 0;
+    if( !skip )
+    {
+        int d[4][4];
+        load_diff<BD, 4>( d, k.fenc + y * k.fs + x, k.fs, k.pred + y * k.ps + x, k.ps );
+        dct4x4_core<BD>( d, s.c );
+        int acc = 0;
+#pragma unroll
+        for( int j = 0; j < 16; j++ )
+        {
+            s.c[j] = sto<BD>( quant_one( s.c[j], k.mf4[j], k.bias4[j] ) );
+            acc |= s.c[j];
+        }
+        s.nzb = acc != 0;
+        if( dec && s.nzb )
+            score = decimate_score<16, 0>( [&]( int i ) { return s.c[ZZF<4>::x( i ) * 4 + ZZF<4>::y( i )]; } );
+    }
+    // the 8x8's decision (macroblock.c:862-905), taken by each of its four lanes
+    s.i_decimate_8x8 = dec ? 0 : 6;
+    s.nnz8x8 = 0;
+#pragma unroll
+    for( int j = 0; j < 4; j++ )
+    {
+        const int nzk = mb_lane( s.nzb, (l & 12) + j ), sk = mb_lane( score, (l & 12) + j );
+        if( nzk )
+        {
+            s.nnz8x8 = 1;
+            if( s.i_decimate_8x8 < 6 )
+                s.i_decimate_8x8 += sk;
+        }
+    }
+    const int contrib = s.nnz8x8 ? s.i_decimate_8x8 : 0;
+    s.plane_score = 0;
+#pragma unroll
+    for( int j = 0; j < 4; j++ )
+        s.plane_score += mb_lane( contrib, 4 * j );
+}
+
+// returns this lane's final non_zero_count
+template <int BD>
+__device__ __forceinline__ bool inter_luma4_finish( const PlaneCtx<BD> &k, int l, Inter4 &s, int i_decimate_mb )
+{
+    const int i8 = l >> 2, i4 = l & 3;
+    const int x = (i8 & 1) * 8 + (i4 & 1) * 4, y = (i8 >> 1) * 8 + (i4 >> 1) * 4;
+    const bool keep = s.nnz8x8 && s.i_decimate_8x8 >= 4 && i_decimate_mb >= 6;
+    const bool nn = keep && s.nzb;
+    int lev[16], res[4][4];
+    zero( lev );
+#pragma unroll
+    for( int yy = 0; yy < 4; yy++ )
+#pragma unroll
+        for( int xx = 0; xx < 4; xx++ )
+            res[yy][xx] = 0;
+    if( nn )
+    {
+#pragma unroll
+        for( int i = 0; i < 16; i++ )
+            lev[i] = s.c[ZZF<4>::x( i ) * 4 + ZZF<4>::y( i )];
+        const int32_t *m = k.dq4 + (k.qp % 6) * 16;
+        const int qb = k.qp / 6 - 4;
+#pragma unroll
+        for( int j = 0; j < 16; j++ )
+            s.c[j] = sto<BD>( dequant_one( s.c[j], m[j], qb ) );
+        idct4_residual<BD>( s.c, res );
+    }
+    put_coefs<BD, 16>( k.lvl + l * 16, lev, k.al );
+    add_block<BD, 4>( k.pred + y * k.ps + x, k.ps, k.recon + y * k.rs + x, k.rs, res );
+    return nn;
+}
+
+// Inter, transform 8 (macroblock.c:806-843), split the same way (the test after the plane: :833).
+// Lanes 0..3 of the plane own the 8x8 blocks; the other lanes take part in the cross-lane reads.
+struct Inter8
+{
+    int c[64];
+    int nzb, score, plane_score;
+};
+
+template <int BD>
+__device__ __forceinline__ void inter_luma8_scores( const PlaneCtx<BD> &k, int l, bool dec, bool skip, Inter8 &s )
+{
+    const int x = (l & 1) * 8, y = ((l >> 1) & 1) * 8;
+    zero( s.c );
+    s.nzb = s.score = 0;
+    if( l < 4 && !skip )
+    {
+        int d[8][8];
+        load_diff<BD, 8>( d, k.fenc + y * k.fs + x, k.fs, k.pred + y * k.ps + x, k.ps );
+        dct8x8_core<BD>( d, s.c );
+        int acc = 0;
+#pragma unroll
+        for( int j = 0; j < 64; j++ )
+        {
+            s.c[j] = sto<BD>( quant_one( s.c[j], k.mf8[j], k.bias8[j] ) );
+            acc |= s.c[j];
+        }
+        s.nzb = acc != 0;
+        if( dec && s.nzb )
+            s.score = decimate_score<64, 0>( [&]( int i ) { return s.c[ZZF<8>::x( i ) * 8 + ZZF<8>::y( i )]; } );
+    }
+    // macroblock.c:813-831
+    s.plane_score = 0;
+#pragma unroll
+    for( int j = 0; j < 4; j++ )
+    {
+        const int nzk = mb_lane( s.nzb, j ), sk = mb_lane( s.score, j );
+        if( dec && nzk )
+            s.plane_score += sk;
+    }
+}
+
+// returns whether this lane's 8x8 block is kept (false on the lanes past 3)
+template <int BD>
+__device__ __forceinline__ bool inter_luma8_finish( const PlaneCtx<BD> &k, int l, bool dec, Inter8 &s, int i_decimate_mb )
+{
+    const int x = (l & 1) * 8, y = ((l >> 1) & 1) * 8;
+    const bool keep = s.nzb && (!dec || (s.score >= 4 && i_decimate_mb >= 6));
+    if( l < 4 )
+    {
+        int lev[64];
+        zero( lev );
+        if( keep )
+        {
+#pragma unroll
+            for( int i = 0; i < 64; i++ )
+                lev[i] = s.c[ZZF<8>::x( i ) * 8 + ZZF<8>::y( i )];
+        }
+        put_coefs<BD, 64>( k.lvl + l * 64, lev, k.al );
+        int res[8][8];
+        if( keep )
+        {
+            const int32_t *m = k.dq8 + (k.qp % 6) * 64;
+            const int qb = k.qp / 6 - 6;
+#pragma unroll
+            for( int j = 0; j < 64; j++ )
+                s.c[j] = sto<BD>( dequant_one( s.c[j], m[j], qb ) );
+            idct8_residual<BD>( s.c, res );
+        }
+        else
+        {
+#pragma unroll
+            for( int yy = 0; yy < 8; yy++ )
+#pragma unroll
+                for( int xx = 0; xx < 8; xx++ )
+                    res[yy][xx] = 0;
+        }
+        add_block<BD, 8>( k.pred + y * k.ps + x, k.ps, k.recon + y * k.rs + x, k.rs, res );
+    }
+    return keep && l < 4;
 }
 
 } // namespace x264hip
