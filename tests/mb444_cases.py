@@ -34,7 +34,8 @@ A = orc._addr
 CQM_IY, CQM_PY, CQM_IC, CQM_PC = range(4)
 LISTS = {"flat": [cb.FLAT16] * 8,
          "distinct": [cb.JVT4I, cb.JVT4P, cb.CQM_TEST4, cb.FLAT16, cb.JVT8I, cb.JVT8P, cb.CQM_TEST8, cb.FLAT16]}
-SHAPES = ((1, 1, 1), (3, 1, 1), (5, 4, 2), (7, 3, 3))            # (mb_width, mb_height, frames)
+SHAPES = ((1, 1, 1), (3, 1, 1), (5, 4, 2), (1, 3, 1), (2, 2, 1), (7, 3, 3))   # (mb_width, mb_height, frames)
+I_ONLY_SHAPES = ((1, 3, 1), (2, 2, 1))                           # for the intra launches' diagonal walk: I pictures only
 CHAIN_SHAPE = (5, 4, 2)
 SEED = 0                                                         # tests/test_cpu_mb444.py holds it to the coverage conditions
 
@@ -500,9 +501,10 @@ def luma_case(case):
 
 def case_keys(bd):
     """what tests/test_gpu_mb444.py runs at one bit depth: every shape as a mixed picture and as
-    an I picture with the flat matrices, and the distinct matrices once each way (the pictures of
-    up to three macroblocks have no intra one when mixed)"""
-    keys = [(bd, w, h, n, "flat", SEED, ai) for ai in (False, True) for w, h, n in SHAPES]
+    an I picture with the flat matrices (I_ONLY_SHAPES: as an I picture), and the distinct matrices
+    once each way (the pictures of up to three macroblocks have no intra one when mixed)"""
+    keys = [(bd, w, h, n, "flat", SEED, ai) for ai in (False, True) for w, h, n in SHAPES
+            if ai or (w, h, n) not in I_ONLY_SHAPES]
     return keys + DISTINCT_KEYS(bd)
 
 

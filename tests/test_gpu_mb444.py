@@ -175,7 +175,8 @@ def test_mb_encode_444_bit_exact(hip, bd, dec, apart):
     """every shape -- 1x1x1 (one wave, no neighbour), 3x1x1, 5x4 x 2 frames, 7x3 x 3 frames (63
     macroblocks: no multiple of the four a workgroup of the inter kernel holds, diagonals of 1..3
     macroblocks per frame) -- as a mixed picture (inter entry, then intra entry) and as an I picture,
-    flat matrices, the output arrays aligned and one element off"""
+    and 1x3x1 and 2x2x1 (one and two macroblocks wide: diagonals that start below row 0) as I
+    pictures, flat matrices, the output arrays aligned and one element off"""
     for i, key in enumerate(k for k in m4.case_keys(bd) if k[4] == "flat"):
         run(hip, key, dec, shift=(i + apart) & 1, apart=apart)
         if not apart:

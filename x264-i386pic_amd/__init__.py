@@ -1409,6 +1409,81 @@ class MbEnc(_c.Structure):
 MBENC_OUTPUTS = ("level", "chroma_dc", "nnz", "cbp", "nz", "flags_out")
 
 
+def _mb_encode(who, e, lead, refusals, pictures, mb_width, mb_height, nframes, qp, mb_flags, modes, quant4,
+               dequant4_mf, quant8, dequant8_mf, b_dct_decimate, qp_table, chroma_qp_index_offset, outputs, luma_dc,
+               outs, keep_outs, stream):
+    """What the four macroblock-encode wrappers share: the validation, the output arrays, the
+    struct and the call x264hip_<depth>_<who>.  e: the entry's ctypes struct, its own scalars set;
+    lead: the tensor whose depth and device the call takes; refusals: [(condition, wording)], the
+    wrapper's own, raised first; pictures: [(field, plane)], a plane (tensor, origin, stride,
+    frame_stride), or for an Mb444 [(field, (luma, chroma))] as _mb444 describes them; modes:
+    [(field, tensor, modes per macroblock, wording)]; outputs: the names of the entry's arrays,
+    luma_dc: that array's shape per macroblock; keep_outs: the keys of `outs` that are not the
+    entry's arrays stay in the result.  Returns the dict of the outputs."""
+    import torch
+    bd = _pix_bd(lead)
+    for refused, wording in refusals:
+        if refused:
+            raise ValueError(f"{who}: {wording}")
+    if (quant8 is None) != (dequant8_mf is None):
+        raise ValueError(f"{who}: quant8 and dequant8_mf come together")
+    if mb_width < 0 or mb_height < 0 or nframes < 0:
+        raise ValueError(f"{who}: negative size")
+    table = chroma_qp_table(bd, chroma_qp_index_offset) if qp_table is None else \
+        np.ascontiguousarray(np.asarray(qp_table, np.uint8))
+    if table.size < 52 + 6 * (bd - 8):
+        raise ValueError(f"{who}: the chroma qp table needs QP_MAX_SPEC + 1 entries")
+    nmb = nframes * mb_width * mb_height
+    if qp.numel() < nmb or mb_flags.numel() < nmb:
+        raise ValueError(f"{who}: qp and mb_flags need one element per macroblock")
+    for field, t, per_mb, wording in modes:
+        if t.dtype != torch.int8 or t.numel() < per_mb * nmb or not t.is_contiguous():
+            raise ValueError(f"{who}: {field} must be a contiguous int8 tensor of {wording} per macroblock")
+    cdt = torch.int16 if bd == 8 else torch.int32
+    per_mb = {"level": ((48, 16), cdt), "chroma_dc": ((2, 8), cdt), "nnz": ((48,), torch.uint8),
+              "cbp": ((), torch.int32), "nz": ((), torch.int32), "flags_out": ((), torch.uint8),
+              "luma_dc": (luma_dc, cdt)}
+    out = {k: v for k, v in (outs or {}).items() if keep_outs or k in outputs}
+    for name in outputs:
+        shape, dt = (nmb, *per_mb[name][0]), per_mb[name][1]
+        if name not in out:
+            out[name] = torch.zeros(shape, dtype=dt, device=lead.device)
+        elif out[name].dtype != dt or out[name].numel() < int(np.prod(shape)) or not out[name].is_contiguous():
+            raise ValueError(f"{who}: {name} must be a contiguous {dt} tensor of {shape}")
+    e.b_dct_decimate = int(bool(b_dct_decimate))
+    e.chroma_qp_table = table.ctypes.data
+    e.quant4_mf, e.quant4_bias, e.dequant4_mf = _ptr(quant4[0]).value, _ptr(quant4[1]).value, _ptr(dequant4_mf).value
+    if quant8 is not None:
+        e.quant8_mf, e.quant8_bias, e.dequant8_mf = _ptr(quant8[0]).value, _ptr(quant8[1]).value, _ptr(dequant8_mf).value
+    for name, pic in pictures:
+        (y, origin, stride, fstride), chroma = pic if isinstance(e, Mb444) else (pic, None)
+        if any(_pix_bd(t) != bd for t in (y, *(chroma[0] if chroma else ()))):
+            raise TypeError(f"{who}: the planes disagree on the bit depth")
+        if chroma:
+            uv, c_origin, c_stride, c_fstride = chroma
+            ptrs = getattr(e, name)
+            ptrs[0] = _ptr(y, origin).value
+            ptrs[1], ptrs[2] = _ptr(uv[0], c_origin).value, _ptr(uv[1], c_origin).value
+            setattr(e, name + "_chroma_stride", c_stride)
+            setattr(e, name + "_chroma_frame_stride", c_fstride)
+        else:
+            setattr(e, name, _ptr(y, origin).value)
+        setattr(e, name + "_stride", stride)
+        setattr(e, name + "_frame_stride", fstride)
+    # (torch gives an empty tensor a NULL pointer; with no macroblock the arrays are not read)
+    dummy = _c.addressof(e)
+    e.qp = _ptr(qp).value or dummy
+    e.mb_flags = _ptr(mb_flags).value or dummy
+    for field, t, _, _ in modes:
+        setattr(e, field, _ptr(t).value or dummy)
+    for name in outputs:
+        setattr(e, name, _ptr(out[name]).value or dummy)
+    fname = f"x264hip_{bd}_{who}"
+    st = _stream() if stream is None else _c.c_void_p(stream.cuda_stream)
+    _rc(getattr(lib(), fname)(_c.byref(e), mb_width, mb_height, nframes, st), fname)
+    return out
+
+
 def mb_encode_inter(fenc, pred, mb_width, mb_height, nframes, qp, mb_flags, quant4, dequant4_mf, quant8=None,
                     dequant8_mf=None, chroma_format=0, fenc_chroma=None, pred_chroma=None, recon=None,
                     recon_chroma=None, b_dct_decimate=True, qp_table=None, chroma_qp_index_offset=0, outs=None):
@@ -1422,58 +1497,20 @@ def mb_encode_inter(fenc, pred, mb_width, mb_height, nframes, qp, mb_flags, quan
     default chroma_qp_table(depth, chroma_qp_index_offset).  outs: {name: tensor} for any of
     MBENC_OUTPUTS to write into (intra macroblocks' elements stay as they are); the others are
     allocated zeroed.  Returns a dict: recon, recon_chroma (the plane tuples) and MBENC_OUTPUTS."""
-    import torch
-    bd = _pix_bd(pred[0])
     cf = int(chroma_format)
-    if cf not in (0, 1, 2):
-        raise ValueError("mb_encode_inter: chroma_format is 0 (luma only), 1 (4:2:0) or 2 (4:2:2)")
-    if cf and (fenc_chroma is None or pred_chroma is None):
-        raise ValueError("mb_encode_inter: the chroma format needs fenc_chroma and pred_chroma")
-    if (quant8 is None) != (dequant8_mf is None):
-        raise ValueError("mb_encode_inter: quant8 and dequant8_mf come together")
-    if mb_width < 0 or mb_height < 0 or nframes < 0:
-        raise ValueError("mb_encode_inter: negative size")
-    table = chroma_qp_table(bd, chroma_qp_index_offset) if qp_table is None else \
-        np.ascontiguousarray(np.asarray(qp_table, np.uint8))
-    if table.size < 52 + 6 * (bd - 8):
-        raise ValueError("mb_encode_inter: the chroma qp table needs QP_MAX_SPEC + 1 entries")
-    nmb = nframes * mb_width * mb_height
-    if qp.numel() < nmb or mb_flags.numel() < nmb:
-        raise ValueError("mb_encode_inter: qp and mb_flags need one element per macroblock")
     recon = pred if recon is None else recon
     recon_chroma = pred_chroma if recon_chroma is None else recon_chroma
-    cdt = torch.int16 if bd == 8 else torch.int32
-    shapes = {"level": ((nmb, 48, 16), cdt), "chroma_dc": ((nmb, 2, 8), cdt), "nnz": ((nmb, 48), torch.uint8),
-              "cbp": ((nmb,), torch.int32), "nz": ((nmb,), torch.int32), "flags_out": ((nmb,), torch.uint8)}
-    out = dict(outs or {})
-    for name, (shape, dt) in shapes.items():
-        if name not in out:
-            out[name] = torch.zeros(shape, dtype=dt, device=pred[0].device)
-        elif out[name].dtype != dt or out[name].numel() < int(np.prod(shape)) or not out[name].is_contiguous():
-            raise ValueError(f"mb_encode_inter: {name} must be a contiguous {dt} tensor of {shape}")
-    e = MbEnc()
-    e.chroma_format, e.b_dct_decimate = cf, int(bool(b_dct_decimate))
-    e.chroma_qp_table = table.ctypes.data
-    e.quant4_mf, e.quant4_bias, e.dequant4_mf = _ptr(quant4[0]).value, _ptr(quant4[1]).value, _ptr(dequant4_mf).value
-    if quant8 is not None:
-        e.quant8_mf, e.quant8_bias, e.dequant8_mf = _ptr(quant8[0]).value, _ptr(quant8[1]).value, _ptr(dequant8_mf).value
     planes = [("fenc", fenc), ("pred", pred), ("recon", recon)]
     if cf:
         planes += [("fenc_chroma", fenc_chroma), ("pred_chroma", pred_chroma), ("recon_chroma", recon_chroma)]
-    for name, (t, origin, stride, fstride) in planes:
-        if _pix_bd(t) != bd:
-            raise TypeError("mb_encode_inter: the planes disagree on the bit depth")
-        setattr(e, name, _ptr(t, origin).value)
-        setattr(e, name + "_stride", stride)
-        setattr(e, name + "_frame_stride", fstride)
-    # (torch gives an empty tensor a NULL pointer; with no macroblock the arrays are not read)
-    dummy = _c.addressof(e)
-    e.qp = _ptr(qp).value or dummy
-    e.mb_flags = _ptr(mb_flags).value or dummy
-    for name in MBENC_OUTPUTS:
-        setattr(e, name, _ptr(out[name]).value or dummy)
-    fname = f"x264hip_{bd}_mb_encode_inter"
-    _rc(getattr(lib(), fname)(_c.byref(e), mb_width, mb_height, nframes, _stream()), fname)
+    e = MbEnc()
+    e.chroma_format = cf
+    out = _mb_encode("mb_encode_inter", e, pred[0],
+                     [(cf not in (0, 1, 2), "chroma_format is 0 (luma only), 1 (4:2:0) or 2 (4:2:2)"),
+                      (cf and (fenc_chroma is None or pred_chroma is None),
+                       "the chroma format needs fenc_chroma and pred_chroma")],
+                     planes, mb_width, mb_height, nframes, qp, mb_flags, [], quant4, dequant4_mf, quant8, dequant8_mf,
+                     b_dct_decimate, qp_table, chroma_qp_index_offset, MBENC_OUTPUTS, None, outs, True, None)
     out["recon"], out["recon_chroma"] = recon, recon_chroma if cf else None
     return out
 
@@ -1512,65 +1549,20 @@ def mb_encode_intra(fenc, recon, mb_width, mb_height, nframes, qp, mb_flags, pre
     MBINTRA_OUTPUTS to write into, for instance the dict mb_encode_inter returned (the two calls
     fill disjoint macroblocks); the others are allocated zeroed.  stream: a torch.cuda.Stream, default
     the current one.  Returns a dict: recon, recon_chroma (the plane tuples) and MBINTRA_OUTPUTS."""
-    import torch
-    bd = _pix_bd(recon[0])
     cf = int(chroma_format)
-    if cf not in (0, 1, 2):
-        raise ValueError("mb_encode_intra: chroma_format is 0 (luma only), 1 (4:2:0) or 2 (4:2:2)")
-    if cf and (fenc_chroma is None or recon_chroma is None or chroma_pred_mode is None):
-        raise ValueError("mb_encode_intra: the chroma format needs fenc_chroma, recon_chroma and chroma_pred_mode")
-    if (quant8 is None) != (dequant8_mf is None):
-        raise ValueError("mb_encode_intra: quant8 and dequant8_mf come together")
-    if mb_width < 0 or mb_height < 0 or nframes < 0:
-        raise ValueError("mb_encode_intra: negative size")
-    table = chroma_qp_table(bd) if qp_table is None else np.ascontiguousarray(np.asarray(qp_table, np.uint8))
-    if table.size < 52 + 6 * (bd - 8):
-        raise ValueError("mb_encode_intra: the chroma qp table needs QP_MAX_SPEC + 1 entries")
-    nmb = nframes * mb_width * mb_height
-    if qp.numel() < nmb or mb_flags.numel() < nmb:
-        raise ValueError("mb_encode_intra: qp and mb_flags need one element per macroblock")
-    if pred_mode.dtype != torch.int8 or pred_mode.numel() < 16 * nmb or not pred_mode.is_contiguous():
-        raise ValueError("mb_encode_intra: pred_mode must be a contiguous int8 tensor of 16 modes per macroblock")
-    if cf and (chroma_pred_mode.dtype != torch.int8 or chroma_pred_mode.numel() < nmb
-               or not chroma_pred_mode.is_contiguous()):
-        raise ValueError("mb_encode_intra: chroma_pred_mode must be a contiguous int8 tensor of one mode per macroblock")
-    cdt = torch.int16 if bd == 8 else torch.int32
-    shapes = {"level": ((nmb, 48, 16), cdt), "chroma_dc": ((nmb, 2, 8), cdt), "nnz": ((nmb, 48), torch.uint8),
-              "cbp": ((nmb,), torch.int32), "nz": ((nmb,), torch.int32), "flags_out": ((nmb,), torch.uint8),
-              "luma_dc": ((nmb, 16), cdt)}
-    out = {k: v for k, v in (outs or {}).items() if k in shapes}
-    for name, (shape, dt) in shapes.items():
-        if name not in out:
-            out[name] = torch.zeros(shape, dtype=dt, device=recon[0].device)
-        elif out[name].dtype != dt or out[name].numel() < int(np.prod(shape)) or not out[name].is_contiguous():
-            raise ValueError(f"mb_encode_intra: {name} must be a contiguous {dt} tensor of {shape}")
-    e = MbIntra()
-    e.chroma_format, e.b_dct_decimate = cf, int(bool(b_dct_decimate))
-    e.chroma_qp_table = table.ctypes.data
-    e.quant4_mf, e.quant4_bias, e.dequant4_mf = _ptr(quant4[0]).value, _ptr(quant4[1]).value, _ptr(dequant4_mf).value
-    if quant8 is not None:
-        e.quant8_mf, e.quant8_bias, e.dequant8_mf = _ptr(quant8[0]).value, _ptr(quant8[1]).value, _ptr(dequant8_mf).value
     planes = [("fenc", fenc), ("recon", recon)]
+    modes = [("pred_mode", pred_mode, 16, "16 modes")]
     if cf:
         planes += [("fenc_chroma", fenc_chroma), ("recon_chroma", recon_chroma)]
-    for name, (t, origin, stride, fstride) in planes:
-        if _pix_bd(t) != bd:
-            raise TypeError("mb_encode_intra: the planes disagree on the bit depth")
-        setattr(e, name, _ptr(t, origin).value)
-        setattr(e, name + "_stride", stride)
-        setattr(e, name + "_frame_stride", fstride)
-    # (torch gives an empty tensor a NULL pointer; with no macroblock the arrays are not read)
-    dummy = _c.addressof(e)
-    e.qp = _ptr(qp).value or dummy
-    e.mb_flags = _ptr(mb_flags).value or dummy
-    e.pred_mode = _ptr(pred_mode).value or dummy
-    if cf:
-        e.chroma_pred_mode = _ptr(chroma_pred_mode).value or dummy
-    for name in MBINTRA_OUTPUTS:
-        setattr(e, name, _ptr(out[name]).value or dummy)
-    fname = f"x264hip_{bd}_mb_encode_intra"
-    st = _stream() if stream is None else _c.c_void_p(stream.cuda_stream)
-    _rc(getattr(lib(), fname)(_c.byref(e), mb_width, mb_height, nframes, st), fname)
+        modes += [("chroma_pred_mode", chroma_pred_mode, 1, "one mode")]
+    e = MbIntra()
+    e.chroma_format = cf
+    out = _mb_encode("mb_encode_intra", e, recon[0],
+                     [(cf not in (0, 1, 2), "chroma_format is 0 (luma only), 1 (4:2:0) or 2 (4:2:2)"),
+                      (cf and (fenc_chroma is None or recon_chroma is None or chroma_pred_mode is None),
+                       "the chroma format needs fenc_chroma, recon_chroma and chroma_pred_mode")],
+                     planes, mb_width, mb_height, nframes, qp, mb_flags, modes, quant4, dequant4_mf, quant8, dequant8_mf,
+                     b_dct_decimate, qp_table, 0, MBINTRA_OUTPUTS, (16,), outs, False, stream)
     out["recon"], out["recon_chroma"] = recon, recon_chroma if cf else None
     return out
 
@@ -1624,64 +1616,15 @@ def _mb444(who, intra, fenc, pred, recon, mb_width, mb_height, nframes, qp, mb_f
            quant8, dequant8_mf, b_dct_decimate, qp_table, chroma_qp_index_offset, outs, stream):
     """the struct and the call of both 4:4:4 entries; a picture is (luma, chroma) with luma =
     (tensor, origin, stride, frame_stride) and chroma = ([U, V], origin, stride, frame_stride)"""
-    import torch
-    for name, pic in (("fenc", fenc), ("pred", pred), ("recon", recon)):
-        if pic is not None and (len(pic) != 2 or len(pic[0]) != 4 or len(pic[1]) != 4 or len(pic[1][0]) != 2):
+    pictures = [(name, pic) for name, pic in (("fenc", fenc), ("pred", pred), ("recon", recon)) if pic is not None]
+    for name, pic in pictures:
+        if len(pic) != 2 or len(pic[0]) != 4 or len(pic[1]) != 4 or len(pic[1][0]) != 2:
             raise ValueError(f"{who}: {name} is (luma, chroma) = ((Y, origin, stride, frame_stride), "
                              "([U, V], origin, stride, frame_stride))")
-    bd = _pix_bd(recon[0][0])
-    if (quant8 is None) != (dequant8_mf is None):
-        raise ValueError(f"{who}: quant8 and dequant8_mf come together")
-    if mb_width < 0 or mb_height < 0 or nframes < 0:
-        raise ValueError(f"{who}: negative size")
-    table = chroma_qp_table(bd, chroma_qp_index_offset) if qp_table is None else \
-        np.ascontiguousarray(np.asarray(qp_table, np.uint8))
-    if table.size < 52 + 6 * (bd - 8):
-        raise ValueError(f"{who}: the chroma qp table needs QP_MAX_SPEC + 1 entries")
-    nmb = nframes * mb_width * mb_height
-    if qp.numel() < nmb or mb_flags.numel() < nmb:
-        raise ValueError(f"{who}: qp and mb_flags need one element per macroblock")
-    if intra and (pred_mode.dtype != torch.int8 or pred_mode.numel() < 16 * nmb or not pred_mode.is_contiguous()):
-        raise ValueError(f"{who}: pred_mode must be a contiguous int8 tensor of 16 modes per macroblock")
-    cdt = torch.int16 if bd == 8 else torch.int32
-    shapes = {"level": ((nmb, 48, 16), cdt), "nnz": ((nmb, 48), torch.uint8), "cbp": ((nmb,), torch.int32),
-              "nz": ((nmb,), torch.int32), "flags_out": ((nmb,), torch.uint8), "luma_dc": ((nmb, 3, 16), cdt)}
-    out = {k: v for k, v in (outs or {}).items() if k in shapes}
-    for name, (shape, dt) in shapes.items():
-        if name not in out:
-            out[name] = torch.zeros(shape, dtype=dt, device=recon[0][0].device)
-        elif out[name].dtype != dt or out[name].numel() < int(np.prod(shape)) or not out[name].is_contiguous():
-            raise ValueError(f"{who}: {name} must be a contiguous {dt} tensor of {shape}")
-    e = Mb444()
-    e.b_dct_decimate = int(bool(b_dct_decimate))
-    e.chroma_qp_table = table.ctypes.data
-    e.quant4_mf, e.quant4_bias, e.dequant4_mf = _ptr(quant4[0]).value, _ptr(quant4[1]).value, _ptr(dequant4_mf).value
-    if quant8 is not None:
-        e.quant8_mf, e.quant8_bias, e.dequant8_mf = _ptr(quant8[0]).value, _ptr(quant8[1]).value, _ptr(dequant8_mf).value
-    for name, pic in (("fenc", fenc), ("pred", pred), ("recon", recon)):
-        if pic is None:
-            continue
-        (y, origin, stride, fstride), (uv, c_origin, c_stride, c_fstride) = pic
-        if any(_pix_bd(t) != bd for t in (y, *uv)):
-            raise TypeError(f"{who}: the planes disagree on the bit depth")
-        ptrs = getattr(e, name)
-        ptrs[0] = _ptr(y, origin).value
-        ptrs[1], ptrs[2] = _ptr(uv[0], c_origin).value, _ptr(uv[1], c_origin).value
-        setattr(e, name + "_stride", stride)
-        setattr(e, name + "_frame_stride", fstride)
-        setattr(e, name + "_chroma_stride", c_stride)
-        setattr(e, name + "_chroma_frame_stride", c_fstride)
-    # (torch gives an empty tensor a NULL pointer; with no macroblock the arrays are not read)
-    dummy = _c.addressof(e)
-    e.qp = _ptr(qp).value or dummy
-    e.mb_flags = _ptr(mb_flags).value or dummy
-    if intra:
-        e.pred_mode = _ptr(pred_mode).value or dummy
-    for name in MB444_OUTPUTS:
-        setattr(e, name, _ptr(out[name]).value or dummy)
-    fname = f"x264hip_{bd}_mb_encode_{'intra' if intra else 'inter'}_444"
-    st = _stream() if stream is None else _c.c_void_p(stream.cuda_stream)
-    _rc(getattr(lib(), fname)(_c.byref(e), mb_width, mb_height, nframes, st), fname)
+    out = _mb_encode(who, Mb444(), recon[0][0], [], pictures, mb_width, mb_height, nframes, qp, mb_flags,
+                     [("pred_mode", pred_mode, 16, "16 modes")] if intra else [], quant4, dequant4_mf, quant8,
+                     dequant8_mf, b_dct_decimate, qp_table, chroma_qp_index_offset, MB444_OUTPUTS, (3, 16), outs, False,
+                     stream)
     out["recon"] = recon
     return out
 

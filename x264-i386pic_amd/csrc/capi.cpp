@@ -1689,48 +1689,82 @@ extern "C" int x264hip_deblock_strength( const x264hip_deblock_strength_t *s, in
                     "deblock_strength" );
 }
 
-// ------------------------------------------------------------ inter MB encode (x264hip_mbenc.h)
-// every argument error is X264HIP_EINVAL before any HIP call; of the pointers only e and
-// e->chroma_qp_table (host memory) are dereferenced
-template <int BD>
-static int mb_encode_inter_entry( const x264hip_mbenc_t *e, int mb_width, int mb_height, int n_frames, void *stream )
+// ------------------------------------------------------------ MB encodes (x264hip_mbenc.h, _mbintra.h, _mb444.h)
+// What an entry states of its own struct for the shared check below: the fields only it has are
+// all there, its limit for the chroma qp table, and one of its own reconstruction planes, chroma
+// strides or coefficient arrays is misaligned.
+struct MbOwn
+{
+    bool present;
+    int cqp_slack;                          // the table's entries are at most QP_MAX_SPEC - cqp_slack
+    bool misaligned;
+};
+
+// The rules the macroblock encodes share, over the fields their structs name alike, then the
+// launch.  Every argument error is X264HIP_EINVAL before any HIP call, and wins over an empty
+// batch; of the pointers only e and e->chroma_qp_table (host memory) are dereferenced.
+// own( e, px, co ) -> MbOwn with the sizes of a pixel and of a dctcoef; name: the entry's, for
+// the error text.
+template <int BD, typename E, typename Own, typename Launch>
+static int mb_encode_entry( const E *e, int mb_width, int mb_height, int n_frames, const char *name, Own own,
+                            Launch launch )
 {
     if( !e || mb_width < 0 || mb_height < 0 || n_frames < 0 )
         return X264HIP_EINVAL;
-    const int cf = e->chroma_format;
-    if( cf < 0 || cf > 2 || !e->chroma_qp_table || !e->quant4_mf || !e->quant4_bias || !e->dequant4_mf || !e->fenc ||
-        !e->pred || !e->recon || !e->qp || !e->mb_flags || !e->level || !e->chroma_dc || !e->nnz || !e->cbp ||
-        !e->nz || !e->flags_out )
-        return X264HIP_EINVAL;
-    if( cf && ( !e->fenc_chroma || !e->pred_chroma || !e->recon_chroma ) )
+    const uintptr_t px = sizeof( typename PT<BD>::pixel ), co = sizeof( typename PT<BD>::dctcoef );
+    const MbOwn o = own( e, px, co );
+    if( !o.present || !e->chroma_qp_table || !e->quant4_mf || !e->quant4_bias || !e->dequant4_mf || !e->qp ||
+        !e->mb_flags || !e->level || !e->nnz || !e->cbp || !e->nz || !e->flags_out )
         return X264HIP_EINVAL;
     const int n8 = !e->quant8_mf + !e->quant8_bias + !e->dequant8_mf;
     if( n8 != 0 && n8 != 3 )
         return X264HIP_EINVAL;
     constexpr int QP_MAX_SPEC = 51 + 6 * (BD - 8);
     for( int q = 0; q <= QP_MAX_SPEC; q++ )
-        if( e->chroma_qp_table[q] > QP_MAX_SPEC - ( cf == 2 ? 3 : 0 ) )
+        if( e->chroma_qp_table[q] > QP_MAX_SPEC - o.cqp_slack )
             return X264HIP_EINVAL;
     const int64_t mbs = (int64_t)n_frames * mb_width * mb_height;
     if( mbs > ( 1 << 28 ) )
         return X264HIP_EINVAL;
     // blocks are stored as whole dwords: outputs on 4-pixel boundaries (the mb_mc rule)
-    const uintptr_t px = sizeof( typename PT<BD>::pixel ), co = sizeof( typename PT<BD>::dctcoef );
-    bool bad = (uintptr_t)e->recon % (4 * px) || e->recon_stride % 4 || e->recon_frame_stride % 4;
-    if( cf )
-        bad |= (uintptr_t)e->recon_chroma % (4 * px) || e->recon_chroma_stride % 4 || e->recon_chroma_frame_stride % 4;
-    bad |= (uintptr_t)e->level % co || (uintptr_t)e->chroma_dc % co || (uintptr_t)e->cbp % 4 || (uintptr_t)e->nz % 4;
-    if( bad )
+    if( o.misaligned || e->recon_stride % 4 || e->recon_frame_stride % 4 || (uintptr_t)e->level % co ||
+        (uintptr_t)e->cbp % 4 || (uintptr_t)e->nz % 4 )
     {
-        snprintf( t_err, sizeof(t_err), "x264hip_mb_encode_inter: misaligned reconstruction plane or output array" );
+        snprintf( t_err, sizeof(t_err), "x264hip_%s: misaligned reconstruction plane or output array", name );
         return X264HIP_EINVAL;
     }
     if( mbs == 0 )
         return X264HIP_OK;
     if( int rc = any_device() )
         return rc;
-    return map_err( launch_mb_encode_inter<BD>( e, mb_width, mb_height, n_frames, (hipStream_t)stream ),
-                    "mb_encode_inter" );
+    return map_err( launch(), name );
+}
+
+// the own part that x264hip_mbenc_t and x264hip_mbintra_t have alike: the format, fenc, recon,
+// chroma_dc and, with chroma, its planes
+template <typename E> static MbOwn mb_own_42x( const E *e, uintptr_t px, uintptr_t co )
+{
+    const int cf = e->chroma_format;
+    MbOwn o;
+    o.present = cf >= 0 && cf <= 2 && e->fenc && e->recon && e->chroma_dc && ( !cf || ( e->fenc_chroma && e->recon_chroma ) );
+    o.cqp_slack = cf == 2 ? 3 : 0;
+    o.misaligned = (uintptr_t)e->recon % (4 * px) || (uintptr_t)e->chroma_dc % co ||
+                   ( cf && ( (uintptr_t)e->recon_chroma % (4 * px) || e->recon_chroma_stride % 4 ||
+                             e->recon_chroma_frame_stride % 4 ) );
+    return o;
+}
+
+template <int BD>
+static int mb_encode_inter_entry( const x264hip_mbenc_t *e, int mb_width, int mb_height, int n_frames, void *stream )
+{
+    return mb_encode_entry<BD>( e, mb_width, mb_height, n_frames, "mb_encode_inter",
+        []( const x264hip_mbenc_t *e, uintptr_t px, uintptr_t co )
+        {
+            MbOwn o = mb_own_42x( e, px, co );
+            o.present = o.present && e->pred && ( !e->chroma_format || e->pred_chroma );
+            return o;
+        },
+        [&] { return launch_mb_encode_inter<BD>( e, mb_width, mb_height, n_frames, (hipStream_t)stream ); } );
 }
 
 extern "C" int x264hip_8_mb_encode_inter( const x264hip_mbenc_t *e, int mb_width, int mb_height, int n_frames,
@@ -1745,50 +1779,19 @@ extern "C" int x264hip_10_mb_encode_inter( const x264hip_mbenc_t *e, int mb_widt
     return mb_encode_inter_entry<10>( e, mb_width, mb_height, n_frames, stream );
 }
 
-// ------------------------------------------------------------ intra MB encode (x264hip_mbintra.h)
-// every argument error is X264HIP_EINVAL before any HIP call; of the pointers only e and
-// e->chroma_qp_table (host memory) are dereferenced.  The launches, one per macroblock
-// anti-diagonal, are launch_mb_encode_intra's loop.
+// (the launches, one per macroblock anti-diagonal, are launch_mb_encode_intra's)
 template <int BD>
 static int mb_encode_intra_entry( const x264hip_mbintra_t *e, int mb_width, int mb_height, int n_frames, void *stream )
 {
-    if( !e || mb_width < 0 || mb_height < 0 || n_frames < 0 )
-        return X264HIP_EINVAL;
-    const int cf = e->chroma_format;
-    if( cf < 0 || cf > 2 || !e->chroma_qp_table || !e->quant4_mf || !e->quant4_bias || !e->dequant4_mf || !e->fenc ||
-        !e->recon || !e->qp || !e->mb_flags || !e->pred_mode || !e->level || !e->chroma_dc || !e->nnz || !e->cbp ||
-        !e->nz || !e->flags_out || !e->luma_dc )
-        return X264HIP_EINVAL;
-    if( cf && ( !e->fenc_chroma || !e->recon_chroma || !e->chroma_pred_mode ) )
-        return X264HIP_EINVAL;
-    const int n8 = !e->quant8_mf + !e->quant8_bias + !e->dequant8_mf;
-    if( n8 != 0 && n8 != 3 )
-        return X264HIP_EINVAL;
-    constexpr int QP_MAX_SPEC = 51 + 6 * (BD - 8);
-    for( int q = 0; q <= QP_MAX_SPEC; q++ )
-        if( e->chroma_qp_table[q] > QP_MAX_SPEC - ( cf == 2 ? 3 : 0 ) )
-            return X264HIP_EINVAL;
-    const int64_t mbs = (int64_t)n_frames * mb_width * mb_height;
-    if( mbs > ( 1 << 28 ) )
-        return X264HIP_EINVAL;
-    // blocks are stored as whole dwords: outputs on 4-pixel boundaries (the mb_mc rule)
-    const uintptr_t px = sizeof( typename PT<BD>::pixel ), co = sizeof( typename PT<BD>::dctcoef );
-    bool bad = (uintptr_t)e->recon % (4 * px) || e->recon_stride % 4 || e->recon_frame_stride % 4;
-    if( cf )
-        bad |= (uintptr_t)e->recon_chroma % (4 * px) || e->recon_chroma_stride % 4 || e->recon_chroma_frame_stride % 4;
-    bad |= (uintptr_t)e->level % co || (uintptr_t)e->chroma_dc % co || (uintptr_t)e->luma_dc % co ||
-           (uintptr_t)e->cbp % 4 || (uintptr_t)e->nz % 4;
-    if( bad )
-    {
-        snprintf( t_err, sizeof(t_err), "x264hip_mb_encode_intra: misaligned reconstruction plane or output array" );
-        return X264HIP_EINVAL;
-    }
-    if( mbs == 0 )
-        return X264HIP_OK;
-    if( int rc = any_device() )
-        return rc;
-    return map_err( launch_mb_encode_intra<BD>( e, mb_width, mb_height, n_frames, (hipStream_t)stream ),
-                    "mb_encode_intra" );
+    return mb_encode_entry<BD>( e, mb_width, mb_height, n_frames, "mb_encode_intra",
+        []( const x264hip_mbintra_t *e, uintptr_t px, uintptr_t co )
+        {
+            MbOwn o = mb_own_42x( e, px, co );
+            o.present = o.present && e->pred_mode && e->luma_dc && ( !e->chroma_format || e->chroma_pred_mode );
+            o.misaligned = o.misaligned || (uintptr_t)e->luma_dc % co;
+            return o;
+        },
+        [&] { return launch_mb_encode_intra<BD>( e, mb_width, mb_height, n_frames, (hipStream_t)stream ); } );
 }
 
 extern "C" int x264hip_8_mb_encode_intra( const x264hip_mbintra_t *e, int mb_width, int mb_height, int n_frames,
@@ -1850,56 +1853,31 @@ extern "C" int x264hip_10_cqm_init444( const uint8_t *const sl[8], int dz_inter,
     return cqm_init<10>( sl, dz_inter, dz_intra, 4, q4m, q4b, q8m, q8b );
 }
 
-// every argument error is X264HIP_EINVAL before any HIP call; of the pointers only e and
-// e->chroma_qp_table (host memory) are dereferenced.  The two entries differ in the fields they
-// need (pred; pred_mode and luma_dc) and in the launcher.
+// The two entries differ in the fields they need (pred; pred_mode and luma_dc) and in the launcher.
 template <int BD>
 static int mb_encode_444_entry( const x264hip_mb444_t *e, int mb_width, int mb_height, int n_frames, void *stream,
                                 bool intra )
 {
-    if( !e || mb_width < 0 || mb_height < 0 || n_frames < 0 )
-        return X264HIP_EINVAL;
-    if( !e->chroma_qp_table || !e->quant4_mf || !e->quant4_bias || !e->dequant4_mf || !e->qp || !e->mb_flags ||
-        !e->level || !e->nnz || !e->cbp || !e->nz || !e->flags_out )
-        return X264HIP_EINVAL;
-    for( int p = 0; p < 3; p++ )
-        if( !e->fenc[p] || !e->recon[p] || ( !intra && !e->pred[p] ) )
-            return X264HIP_EINVAL;
-    if( intra && ( !e->pred_mode || !e->luma_dc ) )
-        return X264HIP_EINVAL;
-    const int n8 = !e->quant8_mf + !e->quant8_bias + !e->dequant8_mf;
-    if( n8 != 0 && n8 != 3 )
-        return X264HIP_EINVAL;
-    constexpr int QP_MAX_SPEC = 51 + 6 * (BD - 8);
-    for( int q = 0; q <= QP_MAX_SPEC; q++ )
-        if( e->chroma_qp_table[q] > QP_MAX_SPEC )
-            return X264HIP_EINVAL;
-    const int64_t mbs = (int64_t)n_frames * mb_width * mb_height;
-    if( mbs > ( 1 << 28 ) )
-        return X264HIP_EINVAL;
-    // blocks are stored as whole dwords: outputs on 4-pixel boundaries (the mb_mc rule)
-    const uintptr_t px = sizeof( typename PT<BD>::pixel ), co = sizeof( typename PT<BD>::dctcoef );
-    bool bad = e->recon_stride % 4 || e->recon_frame_stride % 4 || e->recon_chroma_stride % 4 ||
-               e->recon_chroma_frame_stride % 4;
-    for( int p = 0; p < 3; p++ )
-        bad |= (uintptr_t)e->recon[p] % (4 * px) != 0;
-    bad |= (uintptr_t)e->level % co || (uintptr_t)e->cbp % 4 || (uintptr_t)e->nz % 4 ||
-           ( intra && (uintptr_t)e->luma_dc % co );
-    if( bad )
-    {
-        snprintf( t_err, sizeof(t_err), "x264hip_mb_encode_%s_444: misaligned reconstruction plane or output array",
-                  intra ? "intra" : "inter" );
-        return X264HIP_EINVAL;
-    }
-    if( mbs == 0 )
-        return X264HIP_OK;
-    if( int rc = any_device() )
-        return rc;
-    if( intra )
-        return map_err( launch_mb_encode_intra_444<BD>( e, mb_width, mb_height, n_frames, (hipStream_t)stream ),
-                        "mb_encode_intra_444" );
-    return map_err( launch_mb_encode_inter_444<BD>( e, mb_width, mb_height, n_frames, (hipStream_t)stream ),
-                    "mb_encode_inter_444" );
+    return mb_encode_entry<BD>( e, mb_width, mb_height, n_frames, intra ? "mb_encode_intra_444" : "mb_encode_inter_444",
+        [intra]( const x264hip_mb444_t *e, uintptr_t px, uintptr_t co )
+        {
+            MbOwn o;
+            o.present = !intra || ( e->pred_mode && e->luma_dc );
+            o.cqp_slack = 0;
+            o.misaligned = e->recon_chroma_stride % 4 || e->recon_chroma_frame_stride % 4 ||
+                           ( intra && (uintptr_t)e->luma_dc % co );
+            for( int p = 0; p < 3; p++ )
+            {
+                o.present = o.present && e->fenc[p] && e->recon[p] && ( intra || e->pred[p] );
+                o.misaligned = o.misaligned || (uintptr_t)e->recon[p] % (4 * px);
+            }
+            return o;
+        },
+        [&]
+        {
+            return intra ? launch_mb_encode_intra_444<BD>( e, mb_width, mb_height, n_frames, (hipStream_t)stream )
+                         : launch_mb_encode_inter_444<BD>( e, mb_width, mb_height, n_frames, (hipStream_t)stream );
+        } );
 }
 
 extern "C" int x264hip_8_mb_encode_inter_444( const x264hip_mb444_t *e, int mb_width, int mb_height, int n_frames,

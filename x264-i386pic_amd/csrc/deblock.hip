@@ -445,7 +445,7 @@ hipError_t launch_deblock_frames( const x264hip_deblock_t *d, int mbw, int mbh, 
     using pixel = typename PT<BD>::pixel;
     if( !d || mbw <= 0 || mbh <= 0 || n_frames <= 0 )
         return hipSuccess;
-    constexpr int QP_BD_OFFSET = 6 * (BD - 8), QP_MAX_SPEC = 51 + QP_BD_OFFSET;
+    constexpr int QP_BD_OFFSET = 6 * (BD - 8);
     DbParams<BD> a;
     a.y = (pixel *)d->luma; a.c0 = (pixel *)d->chroma[0]; a.c1 = (pixel *)d->chroma[1];
     a.ys = d->luma_stride; a.yfs = d->luma_frame_stride;
@@ -455,19 +455,12 @@ hipError_t launch_deblock_frames( const x264hip_deblock_t *d, int mbw, int mbh, 
     a.a = d->alpha_c0_offset - QP_BD_OFFSET;
     a.b = d->beta_offset - QP_BD_OFFSET;
     a.qp_thresh = 15 - std::min( a.a, a.b ) - std::max( 0, d->chroma_qp_index_offset );      // deblock.c:383
-    uint8_t cqp[64] = { 0 };
-    memcpy( cqp, d->chroma_qp_table, QP_MAX_SPEC + 1 );
-    memcpy( a.cqp, cqp, sizeof( cqp ) );
+    pack_cqp<BD>( d->chroma_qp_table, a.cqp );
     const int cf = d->chroma_format;
-    for( int dg = 0; dg <= mbw - 1 + 2 * (mbh - 1); dg++ )
+    for_each_diagonal( mbw, mbh, [&]( int dg, int ymin, int count )
     {
-        // the MBs (dg - 2y, y) inside the frame
-        a.d = dg;
-        a.ymin = dg > mbw - 1 ? ( dg - (mbw - 1) + 1 ) >> 1 : 0;
-        a.count = std::min( mbh - 1, dg >> 1 ) - a.ymin + 1;
-        if( a.count <= 0 )
-            continue;
-        const unsigned blocks = (unsigned)a.count * (unsigned)n_frames;
+        a.d = dg; a.ymin = ymin; a.count = count;
+        const unsigned blocks = (unsigned)count * (unsigned)n_frames;
         switch( cf )
         {
             case 0: deblock_go<BD, 0>( a, blocks, stream ); break;
@@ -475,7 +468,7 @@ hipError_t launch_deblock_frames( const x264hip_deblock_t *d, int mbw, int mbh, 
             case 2: deblock_go<BD, 2>( a, blocks, stream ); break;
             default: deblock_go<BD, 3>( a, blocks, stream ); break;
         }
-    }
+    } );
     return hipGetLastError();
 }
 X264HIP_INSTANTIATE( launch_deblock_frames );

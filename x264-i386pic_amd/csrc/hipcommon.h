@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 
 #include "x264hip.h"
 
@@ -405,6 +406,27 @@ namespace x264hip {
 inline hipError_t stream_device( hipStream_t stream, int *dev )
 {
     return stream ? hipStreamGetDevice( stream, dev ) : hipGetDevice( dev );
+}
+
+// h->chroma_qp_table[0 .. QP_MAX_SPEC] (host memory) as a kernel-argument block carries it:
+// entries 0..63, four a word, zeros past the table's end
+template <int BD> inline void pack_cqp( const uint8_t *table, uint32_t ( &out )[16] )
+{
+    uint8_t cqp[64] = { 0 };
+    memcpy( cqp, table, 52 + 6 * (BD - 8) );
+    memcpy( out, cqp, sizeof( cqp ) );
+}
+
+// fn( d, ymin, count ) for every non-empty anti-diagonal x + 2y = d of an mbw x mbh grid, in
+// dependency order: its macroblocks are (d - 2y, y), y = ymin .. ymin + count - 1
+template <typename F> inline void for_each_diagonal( int mbw, int mbh, F fn )
+{
+    for( int d = 0; d < mbw + 2 * (mbh - 1); d++ )
+    {
+        const int ymin = d >= mbw ? (d - mbw + 2) / 2 : 0, ymax = d / 2 < mbh - 1 ? d / 2 : mbh - 1;
+        if( ymax >= ymin )
+            fn( d, ymin, ymax - ymin + 1 );
+    }
 }
 } // namespace x264hip
 

@@ -239,10 +239,8 @@ template <int BD>
 void fill_params( const x264hip_mb444_t *e, int mbw, int mbh, bool intra, Mb444Params<BD> &a )
 {
     using pixel = typename PT<BD>::pixel;
-    using dctcoef = typename PT<BD>::dctcoef;
-    using udctcoef = typename PT<BD>::udctcoef;
-    constexpr int QP_MAX_SPEC = 51 + 6 * (BD - 8);
     memset( &a, 0, sizeof( a ) );
+    fill_mb_params<BD>( e, mbw, mbh, a );
     for( int p = 0; p < 3; p++ )
     {
         a.fenc[p] = (const pixel *)e->fenc[p];
@@ -255,18 +253,9 @@ void fill_params( const x264hip_mb444_t *e, int mbw, int mbh, bool intra, Mb444P
     a.ps[1] = e->pred_chroma_stride; a.pfs[1] = e->pred_chroma_frame_stride;
     a.rs[0] = e->recon_stride; a.rfs[0] = e->recon_frame_stride;
     a.rs[1] = e->recon_chroma_stride; a.rfs[1] = e->recon_chroma_frame_stride;
-    a.q4mf = (const udctcoef *)e->quant4_mf; a.q4b = (const udctcoef *)e->quant4_bias;
-    a.q8mf = (const udctcoef *)e->quant8_mf; a.q8b = (const udctcoef *)e->quant8_bias;
-    a.dq4 = e->dequant4_mf; a.dq8 = e->dequant8_mf;
-    a.qp = e->qp; a.flags = e->mb_flags; a.pmode = e->pred_mode;
-    a.level = (dctcoef *)e->level; a.luma_dc = (dctcoef *)e->luma_dc;
-    a.nnz = e->nnz; a.cbp = e->cbp; a.nz = e->nz; a.flags_out = e->flags_out;
-    a.mbw = mbw; a.mbh = mbh;
-    a.dec = e->b_dct_decimate != 0;
+    a.pmode = e->pred_mode;
+    a.luma_dc = (typename PT<BD>::dctcoef *)e->luma_dc;
     a.al = !(((uintptr_t)e->level | (intra ? (uintptr_t)e->luma_dc : 0)) & 15);
-    uint8_t cqp[64] = { 0 };
-    memcpy( cqp, e->chroma_qp_table, QP_MAX_SPEC + 1 );
-    memcpy( a.cqp, cqp, sizeof( cqp ) );
 }
 
 } // namespace
@@ -293,16 +282,12 @@ hipError_t launch_mb_encode_intra_444( const x264hip_mb444_t *e, int mbw, int mb
         return hipSuccess;
     Mb444Params<BD> a;
     fill_params<BD>( e, mbw, mbh, true, a );
-    // the anti-diagonals x + 2y = d in dependency order; rows ymin .. ymax of diagonal d
-    const int ndiag = mbw + 2 * (mbh - 1);
-    for( int d = 0; d < ndiag; d++ )
+    // one launch per anti-diagonal, in dependency order
+    for_each_diagonal( mbw, mbh, [&]( int d, int ymin, int count )
     {
-        const int ymin = d >= mbw ? (d - mbw + 2) / 2 : 0, ymax = d / 2 < mbh - 1 ? d / 2 : mbh - 1;
-        if( ymax < ymin )
-            continue;
-        a.d = d; a.ymin = ymin; a.count = ymax - ymin + 1; a.nitems = a.count * n_frames;
+        a.d = d; a.ymin = ymin; a.count = count; a.nitems = count * n_frames;
         hipLaunchKernelGGL( ( mb_encode_intra_444_kernel<BD> ), dim3( (unsigned)a.nitems ), dim3( 64 ), 0, stream, a );
-    }
+    } );
     return hipGetLastError();
 }
 X264HIP_INSTANTIATE( launch_mb_encode_intra_444 );

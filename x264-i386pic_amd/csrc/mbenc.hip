@@ -276,13 +276,11 @@ template <int BD>
 hipError_t launch_mb_encode_inter( const x264hip_mbenc_t *e, int mbw, int mbh, int n_frames, hipStream_t stream )
 {
     using pixel = typename PT<BD>::pixel;
-    using dctcoef = typename PT<BD>::dctcoef;
-    using udctcoef = typename PT<BD>::udctcoef;
     const int64_t nmb = (int64_t)n_frames * mbw * mbh;
     if( !e || nmb <= 0 )
         return hipSuccess;
-    constexpr int QP_MAX_SPEC = 51 + 6 * (BD - 8);
     MbEncParams<BD> a;
+    fill_mb_params<BD>( e, mbw, mbh, a );
     a.fenc = (const pixel *)e->fenc; a.fenc_c = (const pixel *)e->fenc_chroma;
     a.pred = (const pixel *)e->pred; a.pred_c = (const pixel *)e->pred_chroma;
     a.recon = (pixel *)e->recon; a.recon_c = (pixel *)e->recon_chroma;
@@ -292,18 +290,9 @@ hipError_t launch_mb_encode_inter( const x264hip_mbenc_t *e, int mbw, int mbh, i
     a.pcs = e->pred_chroma_stride; a.pcfs = e->pred_chroma_frame_stride;
     a.rs = e->recon_stride; a.rfs = e->recon_frame_stride;
     a.rcs = e->recon_chroma_stride; a.rcfs = e->recon_chroma_frame_stride;
-    a.q4mf = (const udctcoef *)e->quant4_mf; a.q4b = (const udctcoef *)e->quant4_bias;
-    a.q8mf = (const udctcoef *)e->quant8_mf; a.q8b = (const udctcoef *)e->quant8_bias;
-    a.dq4 = e->dequant4_mf; a.dq8 = e->dequant8_mf;
-    a.qp = e->qp; a.flags = e->mb_flags;
-    a.level = (dctcoef *)e->level; a.chroma_dc = (dctcoef *)e->chroma_dc;
-    a.nnz = e->nnz; a.cbp = e->cbp; a.nz = e->nz; a.flags_out = e->flags_out;
-    a.mbw = mbw; a.mbh = mbh; a.nmb = (int)nmb;
-    a.dec = e->b_dct_decimate != 0;
+    a.chroma_dc = (typename PT<BD>::dctcoef *)e->chroma_dc;
+    a.nmb = (int)nmb;
     a.al = !(((uintptr_t)e->level | (uintptr_t)e->chroma_dc) & 15);
-    uint8_t cqp[64] = { 0 };
-    memcpy( cqp, e->chroma_qp_table, QP_MAX_SPEC + 1 );
-    memcpy( a.cqp, cqp, sizeof( cqp ) );
     const dim3 grid( (unsigned)((nmb + 15) / 16) ), blk( 256 );
     switch( e->chroma_format )
     {

@@ -2,11 +2,31 @@
 // mb444.hip (both at 4:4:4): the 16-lanes-per-macroblock cross-lane reads, the coefficient stores,
 // the static inlines of encoder/macroblock.c:35-96 with their 2x4 counterparts, one channel of
 // mb_encode_chroma_internal (reference encoder/macroblock.c:259-490) and one luma-coded plane of
-// an inter macroblock (:801-921) over the cores of txdev.h.
+// an inter macroblock (:801-921) over the cores of txdev.h.  Host side: the fill of their
+// kernel-argument blocks.
 #pragma once
 #include "txdev.h"
 
 namespace x264hip {
+
+// Host: what the public structs of the macroblock encodes (x264hip_mbenc_t, x264hip_mbintra_t,
+// x264hip_mb444_t) and the kernel-argument blocks of mbenc.hip, mbintra.hip and mb444.hip name
+// alike, from e into a.  The launcher adds its planes and strides, pred_mode / chroma_pred_mode,
+// luma_dc / chroma_dc and al (the dctcoef outputs it has are 16-byte aligned).
+template <int BD, typename E, typename A> void fill_mb_params( const E *e, int mbw, int mbh, A &a )
+{
+    using dctcoef = typename PT<BD>::dctcoef;
+    using udctcoef = typename PT<BD>::udctcoef;
+    a.q4mf = (const udctcoef *)e->quant4_mf; a.q4b = (const udctcoef *)e->quant4_bias;
+    a.q8mf = (const udctcoef *)e->quant8_mf; a.q8b = (const udctcoef *)e->quant8_bias;
+    a.dq4 = e->dequant4_mf; a.dq8 = e->dequant8_mf;
+    a.qp = e->qp; a.flags = e->mb_flags;
+    a.level = (dctcoef *)e->level;
+    a.nnz = e->nnz; a.cbp = e->cbp; a.nz = e->nz; a.flags_out = e->flags_out;
+    a.mbw = mbw; a.mbh = mbh;
+    a.dec = e->b_dct_decimate != 0;
+    pack_cqp<BD>( e->chroma_qp_table, a.cqp );
+}
 
 // N coefficients to memory: 16-byte stores when the array is 16-byte aligned
 template <int BD, int N>

@@ -316,44 +316,30 @@ hipError_t launch_mb_encode_intra( const x264hip_mbintra_t *e, int mbw, int mbh,
 {
     using pixel = typename PT<BD>::pixel;
     using dctcoef = typename PT<BD>::dctcoef;
-    using udctcoef = typename PT<BD>::udctcoef;
     if( !e || mbw <= 0 || mbh <= 0 || n_frames <= 0 )
         return hipSuccess;
-    constexpr int QP_MAX_SPEC = 51 + 6 * (BD - 8);
     MbIntraParams<BD> a;
+    fill_mb_params<BD>( e, mbw, mbh, a );
     a.fenc = (const pixel *)e->fenc; a.fenc_c = (const pixel *)e->fenc_chroma;
     a.recon = (pixel *)e->recon; a.recon_c = (pixel *)e->recon_chroma;
     a.fs = e->fenc_stride; a.ffs = e->fenc_frame_stride;
     a.fcs = e->fenc_chroma_stride; a.fcfs = e->fenc_chroma_frame_stride;
     a.rs = e->recon_stride; a.rfs = e->recon_frame_stride;
     a.rcs = e->recon_chroma_stride; a.rcfs = e->recon_chroma_frame_stride;
-    a.q4mf = (const udctcoef *)e->quant4_mf; a.q4b = (const udctcoef *)e->quant4_bias;
-    a.q8mf = (const udctcoef *)e->quant8_mf; a.q8b = (const udctcoef *)e->quant8_bias;
-    a.dq4 = e->dequant4_mf; a.dq8 = e->dequant8_mf;
-    a.qp = e->qp; a.flags = e->mb_flags; a.pmode = e->pred_mode; a.cmode = e->chroma_pred_mode;
-    a.level = (dctcoef *)e->level; a.chroma_dc = (dctcoef *)e->chroma_dc; a.luma_dc = (dctcoef *)e->luma_dc;
-    a.nnz = e->nnz; a.cbp = e->cbp; a.nz = e->nz; a.flags_out = e->flags_out;
-    a.mbw = mbw; a.mbh = mbh;
-    a.dec = e->b_dct_decimate != 0;
+    a.pmode = e->pred_mode; a.cmode = e->chroma_pred_mode;
+    a.chroma_dc = (dctcoef *)e->chroma_dc; a.luma_dc = (dctcoef *)e->luma_dc;
     a.al = !(((uintptr_t)e->level | (uintptr_t)e->chroma_dc | (uintptr_t)e->luma_dc) & 15);
-    uint8_t cqp[64] = { 0 };
-    memcpy( cqp, e->chroma_qp_table, QP_MAX_SPEC + 1 );
-    memcpy( a.cqp, cqp, sizeof( cqp ) );
-    // the anti-diagonals x + 2y = d in dependency order; rows ymin .. ymax of diagonal d
-    const int ndiag = mbw + 2 * (mbh - 1);
-    for( int d = 0; d < ndiag; d++ )
+    // one launch per anti-diagonal, in dependency order
+    for_each_diagonal( mbw, mbh, [&]( int d, int ymin, int count )
     {
-        const int ymin = d >= mbw ? (d - mbw + 2) / 2 : 0, ymax = d / 2 < mbh - 1 ? d / 2 : mbh - 1;
-        if( ymax < ymin )
-            continue;
-        a.d = d; a.ymin = ymin; a.count = ymax - ymin + 1; a.nitems = a.count * n_frames;
+        a.d = d; a.ymin = ymin; a.count = count; a.nitems = count * n_frames;
         switch( e->chroma_format )
         {
             case 0: mb_encode_intra_go<BD, 0>( a, stream ); break;
             case 1: mb_encode_intra_go<BD, 1>( a, stream ); break;
             default: mb_encode_intra_go<BD, 2>( a, stream ); break;
         }
-    }
+    } );
     return hipGetLastError();
 }
 X264HIP_INSTANTIATE( launch_mb_encode_intra );
