@@ -62,8 +62,8 @@
  * does not produce, and the plane loop whose i_decimate_mb carries across planes:
  * x264hip_*_mb_encode_inter_444 of x264hip_mb444.h has both); intra
  * macroblocks; lossless, trellis, noise reduction; the P_SKIP / B_SKIP conversion of
- * macroblock.c:953-971 (it needs pskip_mv; the caller has cbp); zigzag_interleave_8x8_cavlc
- * (x264hip_*_zigzag_interleave_batch does it).
+ * macroblock.c:953-971 (it needs pskip_mv: x264hip_mb_skip_convert of x264hip_mbskip.h runs it on
+ * this entry's cbp); zigzag_interleave_8x8_cavlc (x264hip_*_zigzag_interleave_batch does it).
  *
  * Contract: only pixels of [0, 16*mb_width) x [0, 16*mb_height) and the matching chroma area are
  * read or written.  Strides are in pixels (interleaved chroma: in samples of the interleaved

@@ -28,7 +28,8 @@
  *             (mc.c:117-137).  The chroma block of a 4x4 luma block is 2x2 at 4:2:0 (8x4: 4x2,
  *             4x8: 2x4).
  * Not included: the MB_INTERLACED chroma offset, and deriving skip / direct vectors (the caller
- * passes the mv; P_SKIP is a 16x16 list-0 block).
+ * passes the mv; P_SKIP is a 16x16 list-0 block at the vector x264hip_mb_predict_mv_pskip of
+ * x264hip_mbskip.h derives; direct vectors are the caller's).
  *
  * Contract: blocks of one call must not overlap in `pred`; pixels no block covers are not written
  * and `pred` is never read.  The contents of the device arrays are the caller's contract.  With

@@ -36,6 +36,7 @@ __all__ = [
     "mb_encode_inter", "MbEnc", "MBENC_INTRA", "MBENC_T8x8", "MBENC_D16x16", "MBENC_SKIP", "MBENC_OUTPUTS",
     "mb_encode_intra", "MbIntra", "MBINTRA_I16x16", "MBINTRA_OUTPUTS",
     "cqm_init444", "cqm_dequant444", "mb_encode_inter_444", "mb_encode_intra_444", "Mb444", "MB444_OUTPUTS",
+    "mb_predict_mv_pskip", "mb_probe_skip", "mb_skip_convert", "MbSkip",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -341,8 +342,8 @@ def cqm_dequant(scaling_lists, transform_8x8=True):
 
 # ----------------------------------------------------------------- declarations
 # Every function of include/x264hip.h, include/x264hip_mbtree.h, include/x264hip_mc.h,
-# include/x264hip_deblock.h, include/x264hip_mbenc.h, include/x264hip_mbintra.h and
-# include/x264hip_mb444.h, once:
+# include/x264hip_deblock.h, include/x264hip_mbenc.h, include/x264hip_mbintra.h,
+# include/x264hip_mb444.h and include/x264hip_mbskip.h, once:
 # "return:parameters", one letter each, in the struct module's spelling where it has one.
 # tests/test_abi.py checks the first two tables against x264hip.h's prototypes,
 # tests/test_cpu_mbtree.py the third against x264hip_mbtree.h's, tests/test_cpu_mc.py the fourth
@@ -484,6 +485,15 @@ _MB444 = {
 _MB444_PLAIN = {
     "cqm_dequant444": "v:PPP",
 }
+# include/x264hip_mbskip.h: x264hip_8_<name> and x264hip_10_<name>, then x264hip_<name>
+# (tests/test_cpu_mbskip.py checks both against the header's prototypes)
+_MBSKIP = {
+    "mb_probe_skip": "i:PiiiP",
+}
+_MBSKIP_PLAIN = {
+    "mb_predict_mv_pskip": "i:PPiiiPP",
+    "mb_skip_convert": "i:PPPPPiPiiiPP",
+}
 
 
 def _declare(L):
@@ -516,6 +526,11 @@ def _declare(L):
         for bd in (8, 10):
             declare(getattr(L, f"x264hip_{bd}_{name}"), sig)
     for name, sig in _MB444_PLAIN.items():
+        declare(getattr(L, f"x264hip_{name}"), sig)
+    for name, sig in _MBSKIP.items():
+        for bd in (8, 10):
+            declare(getattr(L, f"x264hip_{bd}_{name}"), sig)
+    for name, sig in _MBSKIP_PLAIN.items():
         declare(getattr(L, f"x264hip_{name}"), sig)
 
 
@@ -1657,6 +1672,177 @@ def mb_encode_intra_444(fenc, recon, mb_width, mb_height, nframes, qp, mb_flags,
     return _mb444("mb_encode_intra_444", True, fenc, None, recon, mb_width, mb_height, nframes, qp, mb_flags, pred_mode,
                   quant4, dequant4_mf, quant8, dequant8_mf, b_dct_decimate, qp_table, chroma_qp_index_offset, outs,
                   stream)
+
+
+# ----------------------------------------------------------------- P_SKIP / B_SKIP (include/x264hip_mbskip.h)
+class MbSkip(_c.Structure):
+    """x264hip_mbskip_t"""
+    _fields_ = [("chroma_format", _c.c_int32), ("b_bidir", _c.c_int32), ("chroma_qp_table", _P),
+                ("quant4_mf", _P), ("quant4_bias", _P),
+                ("fenc", _P), ("fenc_stride", _IP), ("fenc_frame_stride", _IP),
+                ("fenc_chroma", _P * 2), ("fenc_chroma_stride", _IP), ("fenc_chroma_frame_stride", _IP),
+                ("ref", McRef), ("ref_stride", _IP), ("ref_frame_stride", _IP),
+                ("ref_chroma_stride", _IP), ("ref_chroma_frame_stride", _IP), ("weight", Weight * 3),
+                ("pskip_mv", _P),
+                ("pred", _P), ("pred_stride", _IP), ("pred_frame_stride", _IP),
+                ("pred_chroma", _P * 2), ("pred_chroma_stride", _IP), ("pred_chroma_frame_stride", _IP),
+                ("qp", _P), ("skip", _P)]
+
+
+def _skip_stream(stream):
+    return _stream() if stream is None else _c.c_void_p(stream.cuda_stream)
+
+
+def _skip_sizes(who, mb_width, mb_height, nframes):
+    if mb_width < 0 or mb_height < 0 or nframes < 0:
+        raise ValueError(f"{who}: negative size")
+    return nframes * mb_width * mb_height
+
+
+def _skip_array(who, name, t, dtype, count):
+    if t.dtype != dtype or t.numel() < count or not t.is_contiguous():
+        raise ValueError(f"{who}: {name} must be a contiguous {dtype} tensor of at least {count} elements")
+    return t
+
+
+def mb_predict_mv_pskip(mv0, ref0, mb_width, mb_height, nframes=1, pskip_mv=None, stream=None):
+    """x264_mb_predict_mv_pskip of every macroblock of nframes frames (x264hip_mb_predict_mv_pskip,
+    include/x264hip_mbskip.h): mv0 int16 [nframes, 4*mbh, 4*mbw, 2] and ref0 int8 [nframes, 2*mbh,
+    2*mbw] as deblock_strength takes them (an intra macroblock: ref -1, mv 0).  Returns pskip_mv
+    int16 [mbs, 2]."""
+    import torch
+    who = "mb_predict_mv_pskip"
+    nmb = _skip_sizes(who, mb_width, mb_height, nframes)
+    _skip_array(who, "mv0", mv0, torch.int16, 32 * nmb)
+    _skip_array(who, "ref0", ref0, torch.int8, 4 * nmb)
+    if pskip_mv is None:
+        pskip_mv = torch.zeros((nmb, 2), dtype=torch.int16, device=mv0.device)
+    _skip_array(who, "pskip_mv", pskip_mv, torch.int16, 2 * nmb)
+    # (torch gives an empty tensor a NULL pointer; with no macroblock the arrays are not read)
+    hold = _c.c_int64()
+    dummy = _c.c_void_p(_c.addressof(hold))
+    args = [_ptr(t) if nmb else dummy for t in (mv0, ref0)]
+    _rc(lib().x264hip_mb_predict_mv_pskip(*args, mb_width, mb_height, nframes, _ptr(pskip_mv) if nmb else dummy,
+                                          _skip_stream(stream)), who)
+    return pskip_mv
+
+
+def mb_probe_skip(fenc, mb_width, mb_height, nframes, qp, quant4, chroma_format=0, fenc_chroma=None, ref=None,
+                  ref_chroma=None, pskip_mv=None, weight=(None, None, None), pred=None, pred_chroma=None,
+                  qp_table=None, chroma_qp_index_offset=0, skip=None, stream=None):
+    """x264_macroblock_probe_skip of every macroblock of nframes frames (x264hip_*_mb_probe_skip,
+    include/x264hip_mbskip.h).  A plane is (tensor, origin, stride, frame_stride) as mb_encode_inter
+    takes it; a chroma plane is the interleaved NV12 / NV16 one, or at chroma_format 3 ([U, V],
+    origin, stride, frame_stride).  qp int8 [mbs]; quant4 = (quant4_mf, quant4_bias), the device
+    copies of cqm_init's tables.
+    The P leg (pred None): ref = ([F, H, V, C], origin, stride) and ref_chroma = (planes, origin,
+    stride) with planes = [NV12 / NV16 tensor] or U's F, H, V, C then V's, as mb_mc takes reference
+    0 of list 0; pskip_mv int16 [mbs, 2] (mb_predict_mv_pskip's); weight[p] = (scale, denom,
+    offset) or None.  The B leg: pred / pred_chroma, the planes mb_mc wrote for the direct
+    prediction.  Returns skip uint8 [mbs] (1 = can be coded as a skip)."""
+    import torch
+    who = "mb_probe_skip"
+    cf = int(chroma_format)
+    if cf not in (0, 1, 2, 3):
+        raise ValueError(f"{who}: chroma_format is 0 (luma only), 1 (4:2:0), 2 (4:2:2) or 3 (4:4:4)")
+    bidir = pred is not None
+    if cf and (fenc_chroma is None or (pred_chroma is None if bidir else ref_chroma is None)):
+        raise ValueError(f"{who}: the chroma format needs fenc_chroma and " + ("pred_chroma" if bidir else "ref_chroma"))
+    if not bidir and (ref is None or pskip_mv is None):
+        raise ValueError(f"{who}: the P leg needs ref and pskip_mv, the B leg pred")
+    nmb = _skip_sizes(who, mb_width, mb_height, nframes)
+    bd = _pix_bd(fenc[0])
+    table = chroma_qp_table(bd, chroma_qp_index_offset) if qp_table is None else \
+        np.ascontiguousarray(np.asarray(qp_table, np.uint8))
+    if table.size < 52 + 6 * (bd - 8):
+        raise ValueError(f"{who}: the chroma qp table needs QP_MAX_SPEC + 1 entries")
+    _skip_array(who, "qp", qp, torch.int8, nmb)
+    if skip is None:
+        skip = torch.zeros(nmb, dtype=torch.uint8, device=fenc[0].device)
+    _skip_array(who, "skip", skip, torch.uint8, nmb)
+    s = MbSkip()
+    s.chroma_format, s.b_bidir = cf, int(bidir)
+    s.chroma_qp_table = table.ctypes.data
+    s.quant4_mf, s.quant4_bias = _ptr(quant4[0]).value, _ptr(quant4[1]).value
+
+    def put(name, plane, chroma):
+        """a luma plane, or a chroma plane / pair of planes, into s.<name>[...]"""
+        t, origin, stride, fstride = plane
+        ts = list(t) if isinstance(t, (list, tuple)) else [t]
+        if any(_pix_bd(p) != bd for p in ts):
+            raise TypeError(f"{who}: the planes disagree on the bit depth")
+        if chroma:
+            for k, p in enumerate(ts):
+                getattr(s, name)[k] = _ptr(p, origin).value
+        else:
+            setattr(s, name, _ptr(t, origin).value)
+        setattr(s, name + "_stride", stride)
+        setattr(s, name + "_frame_stride", fstride)
+
+    put("fenc", fenc, False)
+    if cf:
+        put("fenc_chroma", fenc_chroma, True)
+    if bidir:
+        put("pred", pred, False)
+        if cf:
+            put("pred_chroma", pred_chroma, True)
+    else:
+        planes, origin, stride = ref
+        for k, t in enumerate(planes):
+            s.ref.luma[k] = _ptr(t, origin).value
+        s.ref_stride, s.ref_frame_stride = stride, _frame_stride(*planes)
+        if cf:
+            cplanes, c_origin, c_stride = ref_chroma
+            for k, t in enumerate(cplanes):
+                s.ref.chroma[k] = _ptr(t, c_origin).value
+            s.ref_chroma_stride, s.ref_chroma_frame_stride = c_stride, _frame_stride(*cplanes)
+        for k, w in enumerate(weight):
+            if w is not None:
+                s.weight[k] = Weight(1, *[int(v) for v in w])
+        _skip_array(who, "pskip_mv", pskip_mv, torch.int16, 2 * nmb)
+        s.pskip_mv = _ptr(pskip_mv).value or _c.addressof(s)
+    # (torch gives an empty tensor a NULL pointer; with no macroblock the arrays are not read)
+    s.qp = _ptr(qp).value or _c.addressof(s)
+    s.skip = _ptr(skip).value or _c.addressof(s)
+    name = f"x264hip_{bd}_mb_probe_skip"
+    _rc(getattr(lib(), name)(_c.byref(s), mb_width, mb_height, nframes, _skip_stream(stream)), name)
+    return skip
+
+
+def mb_skip_convert(mb_flags, cbp, mb_width, mb_height, nframes=1, mv0=None, ref0=None, pskip_mv=None, b_bframe=False,
+                    direct=None, flags=None, stream=None):
+    """The P_SKIP / B_SKIP conversion of macroblock.c:953-971 after mb_encode_inter
+    (x264hip_mb_skip_convert, include/x264hip_mbskip.h): mb_flags uint8 [mbs] (MBENC_*) and cbp
+    int32 [mbs] as mb_encode_inter took and wrote them; a P picture (b_bframe False) needs mv0,
+    ref0 and pskip_mv, a B picture direct uint8 [mbs] (nonzero = B_DIRECT).  flags None writes a
+    new array; flags may be mb_flags itself.  Returns flags uint8 [mbs]: mb_flags with MBENC_SKIP
+    also set for the converted macroblocks."""
+    import torch
+    who = "mb_skip_convert"
+    nmb = _skip_sizes(who, mb_width, mb_height, nframes)
+    _skip_array(who, "mb_flags", mb_flags, torch.uint8, nmb)
+    _skip_array(who, "cbp", cbp, torch.int32, nmb)
+    if b_bframe:
+        if direct is None:
+            raise ValueError(f"{who}: a B picture needs direct")
+        _skip_array(who, "direct", direct, torch.uint8, nmb)
+    else:
+        if mv0 is None or ref0 is None or pskip_mv is None:
+            raise ValueError(f"{who}: a P picture needs mv0, ref0 and pskip_mv")
+        _skip_array(who, "mv0", mv0, torch.int16, 32 * nmb)
+        _skip_array(who, "ref0", ref0, torch.int8, 4 * nmb)
+        _skip_array(who, "pskip_mv", pskip_mv, torch.int16, 2 * nmb)
+    if flags is None:
+        flags = torch.zeros(nmb, dtype=torch.uint8, device=mb_flags.device)
+    _skip_array(who, "flags", flags, torch.uint8, nmb)
+    hold = _c.c_int64()
+    dummy = _c.c_void_p(_c.addressof(hold))
+
+    def arg(t):
+        return None if t is None else _ptr(t) if nmb else dummy
+    _rc(lib().x264hip_mb_skip_convert(arg(mb_flags), arg(cbp), arg(mv0), arg(ref0), arg(pskip_mv), int(bool(b_bframe)),
+                                      arg(direct), mb_width, mb_height, nframes, arg(flags), _skip_stream(stream)), who)
+    return flags
 
 
 def plane_stride(width, pad=PAD):

@@ -16,6 +16,7 @@
 #include "x264hip_mbenc.h"
 #include "x264hip_mbintra.h"
 #include "x264hip_mb444.h"
+#include "x264hip_mbskip.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -1902,4 +1903,120 @@ extern "C" int x264hip_10_mb_encode_intra_444( const x264hip_mb444_t *e, int mb_
                                                void *stream )
 {
     return mb_encode_444_entry<10>( e, mb_width, mb_height, n_frames, stream, true );
+}
+
+// ------------------------------------------------------------ P_SKIP / B_SKIP (x264hip_mbskip.h)
+// every argument error is X264HIP_EINVAL before any HIP call, and wins over an empty batch; no
+// device pointer is dereferenced
+static int mbskip_sizes( int mb_width, int mb_height, int n_frames, int64_t *mbs )
+{
+    if( mb_width < 0 || mb_height < 0 || n_frames < 0 )
+        return X264HIP_EINVAL;
+    *mbs = (int64_t)n_frames * mb_width * mb_height;
+    return *mbs > ( 1 << 28 ) ? X264HIP_EINVAL : X264HIP_OK;
+}
+
+extern "C" int x264hip_mb_predict_mv_pskip( const int16_t *mv0, const int8_t *ref0, int mb_width, int mb_height,
+                                            int n_frames, int16_t *pskip_mv, void *stream )
+{
+    int64_t mbs;
+    if( !mv0 || !ref0 || !pskip_mv || mbskip_sizes( mb_width, mb_height, n_frames, &mbs ) )
+        return X264HIP_EINVAL;
+    // an mv is loaded and stored as one dword
+    if( ( (uintptr_t)mv0 | (uintptr_t)pskip_mv ) & 3 )
+    {
+        snprintf( t_err, sizeof(t_err), "x264hip_mb_predict_mv_pskip: mv0 or pskip_mv off a 4-byte boundary" );
+        return X264HIP_EINVAL;
+    }
+    if( mbs == 0 )
+        return X264HIP_OK;
+    if( int rc = any_device() )
+        return rc;
+    return map_err( launch_mb_predict_mv_pskip( mv0, ref0, mb_width, mb_height, n_frames, pskip_mv, (hipStream_t)stream ),
+                    "mb_predict_mv_pskip" );
+}
+
+extern "C" int x264hip_mb_skip_convert( const uint8_t *mb_flags, const int32_t *cbp, const int16_t *mv0,
+                                        const int8_t *ref0, const int16_t *pskip_mv, int b_bframe,
+                                        const uint8_t *direct, int mb_width, int mb_height, int n_frames,
+                                        uint8_t *flags, void *stream )
+{
+    int64_t mbs;
+    if( !mb_flags || !cbp || !flags || mbskip_sizes( mb_width, mb_height, n_frames, &mbs ) )
+        return X264HIP_EINVAL;
+    if( b_bframe ? !direct : ( !mv0 || !ref0 || !pskip_mv ) )
+        return X264HIP_EINVAL;
+    if( ( (uintptr_t)cbp & 3 ) || ( !b_bframe && ( ( (uintptr_t)mv0 | (uintptr_t)pskip_mv ) & 3 ) ) )
+    {
+        snprintf( t_err, sizeof(t_err), "x264hip_mb_skip_convert: cbp, mv0 or pskip_mv off a 4-byte boundary" );
+        return X264HIP_EINVAL;
+    }
+    if( mbs == 0 )
+        return X264HIP_OK;
+    if( int rc = any_device() )
+        return rc;
+    return map_err( launch_mb_skip_convert( mb_flags, cbp, mv0, ref0, pskip_mv, b_bframe, direct, mb_width, mb_height,
+                                            n_frames, flags, (hipStream_t)stream ),
+                    "mb_skip_convert" );
+}
+
+template <int BD>
+static int mb_probe_skip_entry( const x264hip_mbskip_t *s, int mb_width, int mb_height, int n_frames, void *stream )
+{
+    int64_t mbs;
+    if( !s || mbskip_sizes( mb_width, mb_height, n_frames, &mbs ) )
+        return X264HIP_EINVAL;
+    const int cf = s->chroma_format;
+    if( cf < 0 || cf > 3 || !s->chroma_qp_table || !s->quant4_mf || !s->quant4_bias || !s->fenc || !s->qp || !s->skip ||
+        ( cf && !s->fenc_chroma[0] ) || ( cf == 3 && !s->fenc_chroma[1] ) )
+        return X264HIP_EINVAL;
+    const uintptr_t px = sizeof( typename PT<BD>::pixel );
+    if( s->b_bidir )
+    {
+        if( !s->pred || ( cf && !s->pred_chroma[0] ) || ( cf == 3 && !s->pred_chroma[1] ) )
+            return X264HIP_EINVAL;
+    }
+    else
+    {
+        if( !s->pskip_mv )
+            return X264HIP_EINVAL;
+        for( int k = 0; k < 4; k++ )
+            if( !s->ref.luma[k] )
+                return X264HIP_EINVAL;
+        for( int k = 0; k < ( cf == 3 ? 8 : cf ? 1 : 0 ); k++ )
+            if( !s->ref.chroma[k] )
+                return X264HIP_EINVAL;
+        for( int k = 0; k < 3; k++ )
+            if( s->weight[k].weighted && ( s->weight[k].denom < 0 || s->weight[k].denom > 7 ) )
+                return X264HIP_EINVAL;
+        // an mv is loaded as one dword; an interleaved reference plane is read by (U, V) pairs
+        if( ( (uintptr_t)s->pskip_mv & 3 ) ||
+            ( ( cf == 1 || cf == 2 ) && ( (uintptr_t)s->ref.chroma[0] % ( 2 * px ) || s->ref_chroma_stride % 2 ||
+                                          s->ref_chroma_frame_stride % 2 ) ) )
+        {
+            snprintf( t_err, sizeof(t_err), "x264hip_mb_probe_skip: misaligned pskip_mv or interleaved chroma plane" );
+            return X264HIP_EINVAL;
+        }
+    }
+    constexpr int QP_MAX_SPEC = 51 + 6 * (BD - 8);
+    for( int q = 0; q <= QP_MAX_SPEC; q++ )
+        if( s->chroma_qp_table[q] > QP_MAX_SPEC - ( cf == 2 ? 3 : 0 ) )
+            return X264HIP_EINVAL;
+    if( mbs == 0 )
+        return X264HIP_OK;
+    if( int rc = any_device() )
+        return rc;
+    return map_err( launch_mb_probe_skip<BD>( s, mb_width, mb_height, n_frames, (hipStream_t)stream ), "mb_probe_skip" );
+}
+
+extern "C" int x264hip_8_mb_probe_skip( const x264hip_mbskip_t *s, int mb_width, int mb_height, int n_frames,
+                                        void *stream )
+{
+    return mb_probe_skip_entry<8>( s, mb_width, mb_height, n_frames, stream );
+}
+
+extern "C" int x264hip_10_mb_probe_skip( const x264hip_mbskip_t *s, int mb_width, int mb_height, int n_frames,
+                                         void *stream )
+{
+    return mb_probe_skip_entry<10>( s, mb_width, mb_height, n_frames, stream );
 }

@@ -747,3 +747,15 @@ hipError_t launch_mb_encode_inter_444( const x264hip_mb444_t *e, int mbw, int mb
 template <int BD>
 hipError_t launch_mb_encode_intra_444( const x264hip_mb444_t *e, int mbw, int mbh, int n_frames, hipStream_t stream );
 } // namespace x264hip
+
+// P_SKIP / B_SKIP (mbskip.hip; include/x264hip_mbskip.h)
+struct x264hip_mbskip_t;
+namespace x264hip {
+hipError_t launch_mb_predict_mv_pskip( const int16_t *mv0, const int8_t *ref0, int mbw, int mbh, int n_frames,
+                                       int16_t *pskip_mv, hipStream_t stream );
+template <int BD>
+hipError_t launch_mb_probe_skip( const x264hip_mbskip_t *s, int mbw, int mbh, int n_frames, hipStream_t stream );
+hipError_t launch_mb_skip_convert( const uint8_t *mb_flags, const int32_t *cbp, const int16_t *mv0, const int8_t *ref0,
+                                   const int16_t *pskip_mv, int b_bframe, const uint8_t *direct, int mbw, int mbh,
+                                   int n_frames, uint8_t *flags, hipStream_t stream );
+} // namespace x264hip
