@@ -62,7 +62,8 @@
  *
  * Not included: I_PCM; 4:4:4 (x264hip_*_mb_encode_intra_444 of x264hip_mb444.h has it); multiple
  * slices and constrained_intra_pred; lossless, trellis,
- * noise reduction; the i_skip_intra reuse of the analysis' reconstruction; the mode decision.
+ * noise reduction; the i_skip_intra reuse of the analysis' reconstruction.  The mode decision is
+ * x264hip_*_mb_analyse_intra's (x264hip_mbanalyse.h), which ends in this encode.
  *
  * Contract: only pixels of [0, 16*mb_width) x [0, 16*mb_height) of recon and fenc and the matching
  * chroma area are read; only pixels of intra macroblocks are written; an intra macroblock's own

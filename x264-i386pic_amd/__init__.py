@@ -37,6 +37,7 @@ __all__ = [
     "mb_encode_intra", "MbIntra", "MBINTRA_I16x16", "MBINTRA_OUTPUTS",
     "cqm_init444", "cqm_dequant444", "mb_encode_inter_444", "mb_encode_intra_444", "Mb444", "MB444_OUTPUTS",
     "mb_predict_mv_pskip", "mb_probe_skip", "mb_skip_convert", "MbSkip",
+    "mb_analyse_intra", "MbAnalyse", "MBANALYSE_OUTPUTS", "COST_MAX",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -494,6 +495,11 @@ _MBSKIP_PLAIN = {
     "mb_predict_mv_pskip": "i:PPiiiPP",
     "mb_skip_convert": "i:PPPPPiPiiiPP",
 }
+# include/x264hip_mbanalyse.h: x264hip_8_<name> and x264hip_10_<name> (tests/test_cpu_mbanalyse.py
+# checks them against the header's prototypes)
+_MBANALYSE = {
+    "mb_analyse_intra": "i:PiiiP",
+}
 
 
 def _declare(L):
@@ -532,6 +538,9 @@ def _declare(L):
             declare(getattr(L, f"x264hip_{bd}_{name}"), sig)
     for name, sig in _MBSKIP_PLAIN.items():
         declare(getattr(L, f"x264hip_{name}"), sig)
+    for name, sig in _MBANALYSE.items():
+        for bd in (8, 10):
+            declare(getattr(L, f"x264hip_{bd}_{name}"), sig)
 
 
 # ----------------------------------------------------------------- CQM
@@ -1843,6 +1852,89 @@ def mb_skip_convert(mb_flags, cbp, mb_width, mb_height, nframes=1, mv0=None, ref
     _rc(lib().x264hip_mb_skip_convert(arg(mb_flags), arg(cbp), arg(mv0), arg(ref0), arg(pskip_mv), int(bool(b_bframe)),
                                       arg(direct), mb_width, mb_height, nframes, arg(flags), _skip_stream(stream)), who)
     return flags
+
+
+# ----------------------------------------------------------------- intra mode decision (include/x264hip_mbanalyse.h)
+COST_MAX = 1 << 28
+
+
+class MbAnalyse(_c.Structure):
+    """x264hip_mbanalyse_t"""
+    _fields_ = MbIntra._fields_ + [("slice_type", _c.c_int32), ("i_subpel_refine", _c.c_int32), ("b_i4x4", _c.c_int32),
+                                   ("b_i8x8", _c.c_int32), ("b_chroma_me", _c.c_int32), ("lambda_tab", _P),
+                                   ("try_intra", _P), ("satd_inter", _P), ("fast_intra", _P), ("mb_flags_out", _P),
+                                   ("cost", _P)]
+
+
+MBANALYSE_OUTPUTS = MBINTRA_OUTPUTS + ("mb_flags_out", "cost")
+
+
+def mb_analyse_intra(fenc, recon, mb_width, mb_height, nframes, qp, mb_flags, try_intra, pred_mode, lambda_tab, quant4,
+                     dequant4_mf, quant8=None, dequant8_mf=None, chroma_format=0, fenc_chroma=None, recon_chroma=None,
+                     chroma_pred_mode=None, slice_type=0, i_subpel_refine=5, b_i4x4=True, b_i8x8=True, b_chroma_me=False,
+                     satd_inter=None, fast_intra=None, b_dct_decimate=1, qp_table=None, outs=None, stream=None):
+    """x264_mb_analyse_intra of the macroblocks try_intra marks, then x264_macroblock_encode of those
+    that come out intra and of the given-mode intra macroblocks (x264hip_*_mb_analyse_intra,
+    include/x264hip_mbanalyse.h), in mb_encode_intra's place.  Planes, qp, mb_flags, the tables,
+    qp_table, outs and stream as mb_encode_intra.  try_intra uint8 [mbs]; pred_mode int8 [mbs][16]
+    and chroma_pred_mode int8 [mbs] are read for given-mode macroblocks and written for decided
+    ones; lambda_tab: x264_lambda_tab (host uint16 array, QP_MAX_SPEC + 1 entries); slice_type 0 I,
+    1 P, 2 B; satd_inter int32 [mbs] (P / B pictures); fast_intra uint8 [mbs] or None.  outs may
+    also name mb_flags_out (uint8 [mbs], may be mb_flags itself) and cost (int32 [mbs][4]).
+    Returns a dict: recon, recon_chroma, pred_mode, chroma_pred_mode and MBANALYSE_OUTPUTS."""
+    import torch
+    who = "mb_analyse_intra"
+    cf = int(chroma_format)
+    planes = [("fenc", fenc), ("recon", recon)]
+    modes = [("pred_mode", pred_mode, 16, "16 modes")]
+    if cf in (1, 2) and None not in (fenc_chroma, recon_chroma, chroma_pred_mode):
+        planes += [("fenc_chroma", fenc_chroma), ("recon_chroma", recon_chroma)]
+        modes += [("chroma_pred_mode", chroma_pred_mode, 1, "one mode")]
+    bd = _pix_bd(recon[0])
+    lam = np.ascontiguousarray(np.asarray(lambda_tab, np.uint16))
+    nmb = max(nframes * mb_width * mb_height, 0)
+    dev = recon[0].device
+
+    def short(t, dt, n):
+        return t is not None and (t.dtype != dt or t.numel() < n or not t.is_contiguous())
+    outs = dict(outs or {})
+    extra = {"mb_flags_out": outs.pop("mb_flags_out", None), "cost": outs.pop("cost", None)}
+    e = MbAnalyse()
+    e.chroma_format = cf
+    e.slice_type, e.i_subpel_refine = int(slice_type), int(i_subpel_refine)
+    e.b_i4x4, e.b_i8x8, e.b_chroma_me = int(bool(b_i4x4)), int(bool(b_i8x8)), int(bool(b_chroma_me))
+    e.lambda_tab = lam.ctypes.data
+    refusals = [(cf not in (0, 1, 2), "chroma_format is 0 (luma only), 1 (4:2:0) or 2 (4:2:2)"),
+                (cf and (fenc_chroma is None or recon_chroma is None or chroma_pred_mode is None),
+                 "the chroma format needs fenc_chroma, recon_chroma and chroma_pred_mode"),
+                (lam.size < 52 + 6 * (bd - 8), "lambda_tab needs QP_MAX_SPEC + 1 entries"),
+                (e.slice_type not in (0, 1, 2), "slice_type is 0 (I), 1 (P) or 2 (B)"),
+                (not 2 <= e.i_subpel_refine <= 5, "i_subpel_refine is 2..5"),
+                (e.b_i8x8 and quant8 is None, "b_i8x8 needs quant8 and dequant8_mf"),
+                (e.slice_type != 0 and satd_inter is None, "a P / B picture needs satd_inter"),
+                (short(try_intra, torch.uint8, nmb), "try_intra must be a contiguous uint8 tensor, one element per macroblock"),
+                (short(satd_inter, torch.int32, nmb), "satd_inter must be a contiguous int32 tensor, one element per macroblock"),
+                (short(fast_intra, torch.uint8, nmb), "fast_intra must be a contiguous uint8 tensor, one element per macroblock"),
+                (short(extra["mb_flags_out"], torch.uint8, nmb), "mb_flags_out must be a contiguous uint8 tensor, one element per macroblock"),
+                (short(extra["cost"], torch.int32, 4 * nmb), "cost must be a contiguous int32 tensor of four elements per macroblock")]
+    if extra["mb_flags_out"] is None:
+        extra["mb_flags_out"] = mb_flags.clone() if nmb else torch.zeros(0, dtype=torch.uint8, device=dev)
+    if extra["cost"] is None:
+        extra["cost"] = torch.zeros((nmb, 4), dtype=torch.int32, device=dev)
+    # (torch gives an empty tensor a NULL pointer; with no macroblock the arrays are not read)
+    dummy = _c.addressof(e)
+    e.try_intra = _ptr(try_intra).value or dummy
+    e.satd_inter = None if satd_inter is None else _ptr(satd_inter).value or dummy
+    e.fast_intra = None if fast_intra is None else _ptr(fast_intra).value or dummy
+    e.mb_flags_out = _ptr(extra["mb_flags_out"]).value or dummy
+    e.cost = _ptr(extra["cost"]).value or dummy
+    out = _mb_encode(who, e, recon[0], refusals, planes, mb_width, mb_height, nframes, qp, mb_flags, modes, quant4,
+                     dequant4_mf, quant8, dequant8_mf, b_dct_decimate, qp_table, 0, MBINTRA_OUTPUTS, (16,), outs, False,
+                     stream)
+    out.update(extra)
+    out["recon"], out["recon_chroma"] = recon, recon_chroma if cf else None
+    out["pred_mode"], out["chroma_pred_mode"] = pred_mode, chroma_pred_mode if cf else None
+    return out
 
 
 def plane_stride(width, pad=PAD):

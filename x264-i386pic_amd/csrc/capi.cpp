@@ -17,6 +17,7 @@
 #include "x264hip_mbintra.h"
 #include "x264hip_mb444.h"
 #include "x264hip_mbskip.h"
+#include "x264hip_mbanalyse.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -1805,6 +1806,37 @@ extern "C" int x264hip_10_mb_encode_intra( const x264hip_mbintra_t *e, int mb_wi
                                            void *stream )
 {
     return mb_encode_intra_entry<10>( e, mb_width, mb_height, n_frames, stream );
+}
+
+// the intra mode decision (x264hip_mbanalyse.h): mb_encode_intra's rules over the fields the two
+// structs name alike, then its own
+template <int BD>
+static int mb_analyse_intra_entry( const x264hip_mbanalyse_t *e, int mb_width, int mb_height, int n_frames, void *stream )
+{
+    return mb_encode_entry<BD>( e, mb_width, mb_height, n_frames, "mb_analyse_intra",
+        []( const x264hip_mbanalyse_t *e, uintptr_t px, uintptr_t co )
+        {
+            MbOwn o = mb_own_42x( e, px, co );
+            o.present = o.present && e->pred_mode && e->luma_dc && ( !e->chroma_format || e->chroma_pred_mode ) &&
+                        e->lambda_tab && e->try_intra && e->cost && e->mb_flags_out &&
+                        e->slice_type >= 0 && e->slice_type <= 2 && e->i_subpel_refine >= 2 && e->i_subpel_refine <= 5 &&
+                        ( e->slice_type == 0 || e->satd_inter ) && ( !e->b_i8x8 || e->quant8_mf );
+            o.misaligned = o.misaligned || (uintptr_t)e->luma_dc % co || (uintptr_t)e->cost % 4;
+            return o;
+        },
+        [&] { return launch_mb_analyse_intra<BD>( e, mb_width, mb_height, n_frames, (hipStream_t)stream ); } );
+}
+
+extern "C" int x264hip_8_mb_analyse_intra( const x264hip_mbanalyse_t *a, int mb_width, int mb_height, int n_frames,
+                                           void *stream )
+{
+    return mb_analyse_intra_entry<8>( a, mb_width, mb_height, n_frames, stream );
+}
+
+extern "C" int x264hip_10_mb_analyse_intra( const x264hip_mbanalyse_t *a, int mb_width, int mb_height, int n_frames,
+                                            void *stream )
+{
+    return mb_analyse_intra_entry<10>( a, mb_width, mb_height, n_frames, stream );
 }
 
 // dequant4_mf / dequant8_mf of x264_cqm_init, reference common/set.c:31-39,

@@ -739,6 +739,13 @@ template <int BD>
 hipError_t launch_mb_encode_intra( const x264hip_mbintra_t *e, int mbw, int mbh, int n_frames, hipStream_t stream );
 } // namespace x264hip
 
+// the intra mode decision (mbanalyse.hip; include/x264hip_mbanalyse.h)
+struct x264hip_mbanalyse_t;
+namespace x264hip {
+template <int BD>
+hipError_t launch_mb_analyse_intra( const x264hip_mbanalyse_t *e, int mbw, int mbh, int n_frames, hipStream_t stream );
+} // namespace x264hip
+
 // the two at 4:4:4 (mb444.hip; include/x264hip_mb444.h)
 struct x264hip_mb444_t;
 namespace x264hip {
