@@ -377,3 +377,52 @@ ALL = ACTIVE + SHAPES + LOW_QP
 def case_id(k):
     bd, cf, mbw, mbh, nf, seed, off, lo, hi, sl, cqio = k
     return "%dbit-cf%d-%dx%dx%d-o%d,%d-qp%d..%d%s" % (bd, cf, mbw, mbh, nf, off[0], off[1], lo, hi, "-slices" if sl else "")
+
+
+# ------------------------------------------------------------------ what the GPU tests compare
+STRENGTH_SHAPES = ((5, 4, 2), (24, 14, 1))
+# The boundary pictures of deblock_frames, (what is pinned, key): 2x2 macroblocks at the foot of the
+# qp range where alpha and beta are small (4..15 and 2..6 times the depth's scale), so that the
+# steps of picture() -- block offsets in +-5, noise in +-1 -- land on them, one below and one above.
+# At each depth these pictures alone tell every flipped alpha / beta / tc0 comparison of the line
+# filters from the checker (tests/test_cpu_deblock.py); the seeds were found by search.
+def _low(bd, cf, seed):
+    lo = 16 + 6 * (bd - 8)
+    return key(bd, cf, 2, 2, seed=seed, qp_lo=lo, qp_hi=lo + 11)
+
+
+BOUNDARY = [("alpha / beta / tc0 ties, %d bit, format %d, seed %d" % (bd, cf, seed), _low(bd, cf, seed))
+            for bd, cf, seed in ((8, 1, 22), (8, 1, 21), (8, 2, 24), (8, 3, 28), (10, 2, 24), (10, 1, 20), (10, 3, 28))]
+# deblock_strength: vector steps of exactly 4 (and mvy_limit) next to 3 and less, on one small field each way
+BOUNDARY_STRENGTH = [("mv steps at the limit", (2, 2, 1, bf), lim) for bf in (False, True) for lim in (4, 2)]
+GPU_GROUPS = ("frames", "low_qp", "slices", "strength", "boundary")
+
+
+def boundary_keys():
+    return [e[1] for e in BOUNDARY]
+
+
+def gpu_keys(group=None):
+    """every entry tests/test_gpu_deblock.py compares with the device value for value, which is the
+    list the boundary mutants of tests/test_cpu_mutants.py are held to: ("frames", key) for
+    deblock_frames, ("strength", (mbw, mbh, nf, bframe), mvy_limit) for deblock_strength.  group:
+    one of GPU_GROUPS (one test function each)."""
+    keys = {"frames": [("frames", k) for k in MAIN + FORMATS + SHAPES + FRAMES + LONG + TOP],
+            "low_qp": [("frames", k) for k in LOW_QP], "slices": [("frames", k) for k in SLICES],
+            "strength": [("strength", sh + (bf,), lim) for lim in (4, 2) for bf in (False, True) for sh in STRENGTH_SHAPES],
+            "boundary": [("frames", k) for k in boundary_keys()] + [("strength",) + tuple(e[1:]) for e in BOUNDARY_STRENGTH]}
+    return [e for g in GPU_GROUPS if group in (None, g) for e in keys[g]]
+
+
+def gpu_expected(entry):
+    """what the device's output of a gpu_keys() entry is compared with"""
+    if entry[0] == "frames":
+        return expected(entry[1])
+    s = make_strength_case(*entry[1])
+    return deblock_strength_py(s.nz, s.mb_flags, s.mv, s.ref, s.mbw, s.mbh, s.nf, entry[2])
+
+
+def key_size(entry):
+    """macroblocks of a gpu_keys() entry: what it costs"""
+    k = entry[1]
+    return k[2] * k[3] * k[4] if entry[0] == "frames" else k[0] * k[1] * k[2] // 8 + 1

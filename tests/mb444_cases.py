@@ -427,14 +427,44 @@ def inverse_of(bd, T, t8, cat, qp, lev, grey):
     return fdec.reshape(16, FDEC)[:, :16].astype(np.int64)
 
 
+def _boundary_case(bd, mbw, mbh, nframes, cqm, recipe, key):
+    """one inter macroblock per entry (qp, mb_flags, rects, waves) of `recipe`: the three planes mid
+    grey, pred = fenc + mbenc_cases' rectangles and waves (plane 0 / 1 / 2 = Y / U / V, all 16x16).
+    The decimate score runs on from plane to plane (macroblock.c:806-920 inside the plane loop), so
+    a plane is kept or dropped by what it and the planes before it add up to."""
+    n = nframes * mbw * mbh
+    assert n == len(recipe)
+    grey = 128 << (bd - 8)
+    res = [np.zeros((nframes, 16 * mbh, 16 * mbw), np.int64) for _ in range(3)]
+    for mb, (q, fl, rects, waves) in enumerate(recipe):
+        f, r = divmod(mb, mbw * mbh)
+        my, mx = divmod(r, mbw)
+        for plane, y, x, h, w, a in rects:
+            assert y + h <= 16 and x + w <= 16
+            res[plane][f, 16 * my + y:16 * my + y + h, 16 * mx + x:16 * mx + x + w] += a
+        for plane, y, x, u, v, c in waves:
+            res[plane][f, 16 * my + y:16 * my + y + 4, 16 * mx + x:16 * mx + x + 4] += c * np.outer(mc.H4[u], mc.H4[v])
+    pdt = orc.pixel_dtype(bd)
+    assert all(0 <= grey + a.min() and grey + a.max() < (1 << bd) for a in res)
+    return types.SimpleNamespace(
+        bd=bd, mbw=mbw, mbh=mbh, nframes=nframes, nmb=n, cqm=cqm, all_intra=False,
+        fenc=[np.full_like(a, grey).astype(pdt) for a in res], pred=[(grey + a).astype(pdt) for a in res],
+        qp=np.array([r[0] for r in recipe], np.int8), flags=np.array([r[1] for r in recipe], np.uint8),
+        klass=np.full((n, 3), -1, np.int32), pred_mode=np.zeros((n, 16), np.int8), qp_table=mc.chroma_qp_table(bd), key=key)
+
+
 @functools.lru_cache(maxsize=None)
-def make_case(bd, mbw, mbh, nframes, cqm="flat", seed=0, all_intra=False):
+def make_case(bd, mbw, mbh, nframes, cqm="flat", seed=0, all_intra=False, recipe=None):
     """Seeded inputs.  Plane 0, qp, mb_flags and the intra types and modes are
     mbintra_cases.make_case's luma-only case; U and V get a texture of their own and, per plane, a
     residual class of mbenc_cases.make_case scaled to the chroma qp (a full-scale checker wherever
     luma has one).  In pictures of more than three macroblocks about a third of the coded inter
     macroblocks are CARRY: all three planes flat mid grey plus the inverse transform of
-    carry_levels at qp >= 24 + 6 * (bd - 8).  all_intra: the quiet last two rows in all planes."""
+    carry_levels at qp >= 24 + 6 * (bd - 8).  all_intra: the quiet last two rows in all planes.
+    recipe: the boundary picture, see _boundary_case."""
+    if recipe is not None:
+        return _boundary_case(bd, mbw, mbh, nframes, cqm, BOUNDARY_RECIPE if recipe == "boundary" else recipe,
+                              (bd, mbw, mbh, nframes, cqm, seed, all_intra, recipe))
     base = mi.make_case(bd, 0, mbw, mbh, nframes, "flat", seed, all_intra)
     rng = np.random.default_rng([bd, mbw, mbh, nframes, seed, int(all_intra), 444])
     T = tables(bd, cqm)
@@ -510,3 +540,50 @@ def case_keys(bd):
 
 def DISTINCT_KEYS(bd):
     return [(bd, 7, 3, 3, "distinct", SEED, False), (bd, 5, 4, 2, "distinct", SEED, True)]
+
+
+def _on_plane(p, items):
+    return tuple((p,) + it[1:] for it in items)
+
+
+_L4 = (((0, 4, 0, 4, 4, -2),), ((0, 0, 12, 0, 2, -1), (0, 0, 0, 0, 1, 1)))        # mbenc_cases' "4x4 transform, macroblock score = 6"
+# The boundary macroblocks, (what is pinned, (qp, mb_flags, rects, waves)): the decimate score that runs
+# on through the planes exactly 6 when plane 0, 1 or 2 ends, nothing in the other planes.  The
+# flipped comparison (tests/mutants.py) drops that plane.  Found by search over one wave per plane.
+BOUNDARY = (
+    ("8x8 transform: score = 6 after plane 0", (22, T8, (), ((0, 12, 8, 1, 1, 2),))),
+    ("8x8 transform: score = 6 after plane 1", (17, T8, (), ((1, 12, 4, 1, 1, 1),))),
+    ("8x8 transform: score = 6 after plane 2", (17, T8, (), ((2, 8, 8, 1, 1, -1),))),
+    ("4x4 transform: score = 6 after plane 0", (17, 0, _L4[0], _L4[1])),
+    ("4x4 transform: score = 6 after plane 1", (17, 0, _on_plane(1, _L4[0]), _on_plane(1, _L4[1]))),
+    ("4x4 transform: score = 6 after plane 2", (17, 0, _on_plane(2, _L4[0]), _on_plane(2, _L4[1]))),
+    ("8x8 transform: 1 carried over from plane 0 and 5 of plane 2's own = 6: plane 2 kept",
+     (22, T8, (), ((0, 0, 8, 2, 1, -1), (0, 4, 8, 2, 0, -3), (1, 12, 0, 2, 0, 3), (2, 0, 12, 1, 1, 1), (2, 4, 4, 1, 2, -3)))),
+    ("nothing to code", (26, 0, (), ())),
+)
+BOUNDARY_RECIPE = tuple(e for _, e in BOUNDARY)
+
+
+def boundary_keys():
+    """the boundary macroblocks as a 4x2 picture per bit depth"""
+    return [(bd, 4, 2, 1, "flat", SEED, False, "boundary") for bd in (8, 10)]
+
+
+GPU_GROUPS = ("shapes", "distinct", "boundary")
+
+
+def gpu_keys(group=None, **where):
+    """every (key, dec) tests/test_gpu_mb444.py compares with the device byte for byte, which is the
+    list the boundary mutants of tests/test_cpu_mutants.py are held to.  group: one of GPU_GROUPS
+    (one test function each); where: bd / dec of one parametrised case of that function."""
+    keys = {"shapes": [(k, dec) for bd in (8, 10) for dec in (0, 1) for k in case_keys(bd) if k[4] == "flat"],
+            "distinct": [(k, 1) for bd in (8, 10) for k in DISTINCT_KEYS(bd)],
+            "boundary": [(k, 1) for k in boundary_keys()]}
+    keys = [kd for g in GPU_GROUPS if group in (None, g) for kd in keys[g]]
+    pick = {"bd": lambda kd: kd[0][0], "dec": lambda kd: kd[1]}
+    return [kd for kd in keys if all(pick[n](kd) == v for n, v in where.items())]
+
+
+def key_size(kd):
+    """macroblocks of a gpu_keys() entry: what its expected() costs"""
+    return kd[0][1] * kd[0][2] * kd[0][3]

@@ -158,6 +158,7 @@ def i4x4_block(bd, idx, n4, i_pred_mode, lam, fenc, fdec, cnt):
             if i_pred_mode == fix4(i_mode):
                 i_satd -= lam * 3
                 cnt["i4_pred_bonus"] += 1
+                cnt["i4_bonus_satd", mc._side(i_satd, 0)] += 1
                 if i_satd <= 0:
                     i_best, best = i_satd, i_mode
                     cnt["i4_le0_break"] += 1
@@ -195,6 +196,7 @@ def i8x8_block(bd, idx, n8, i_pred_mode, lam, fenc, fdec, cnt):
     for i_mode in predict_mode:
         if i_mode < 0:
             break
+        cnt["i8_best", mc._side(i_best, 0)] += 1
         if not i_best >= 0:
             cnt["i8_best_guard_stop"] += 1
             break
@@ -228,6 +230,7 @@ def analyse_chroma(bd, cf, lam, nb, fenc_c, fdec_c, cnt):
             if i_mode < 0:
                 break
             i_satd = satdu[i_mode] + satdv[i_mode] + lam * UE_SIZE[i_mode]
+            cnt["chroma_x3_cost", mc._side(i_satd, i_satd_chroma)] += 1
             if i_satd < i_satd_chroma:
                 i_satd_chroma, best = i_satd, i_mode
     else:
@@ -240,6 +243,7 @@ def analyse_chroma(bd, cf, lam, nb, fenc_c, fdec_c, cnt):
             i_satd = (orc.cmp(bd, "satd", pix, fenc_c, 0, FENC, fdec_c, OY, FDEC) +
                       orc.cmp(bd, "satd", pix, fenc_c, 8, FENC, fdec_c, OY + 16, FDEC) +
                       lam * UE_SIZE[CHROMA_PRED_MODE_FIX[i_mode]])
+            cnt["chroma_list_cost", mc._side(i_satd, i_satd_chroma)] += 1
             if i_satd < i_satd_chroma:
                 i_satd_chroma, best = i_satd, i_mode
     return i_satd_chroma, best
@@ -258,6 +262,7 @@ def i4x4_pass(bd, T, qp, lam, nb, nm, i_cost, i_satd_thresh, fenc, fdec, cnt):
         cache[idx] = mode
         costs.append(i_best + 3 * lam)
         i_cost += i_best + 3 * lam
+        cnt["i4_cost", mc._side(i_cost, i_satd_thresh), int(idx == 15)] += 1
         if i_cost > i_satd_thresh or idx == 15:
             break
         trial_i4x4(bd, T, qp, mode, idx, fenc, fdec)
@@ -291,7 +296,7 @@ def analyse_intra(bd, T, cfg, qp, lam, nb, nm, i_satd_inter, b_fast_intra, fenc,
     """mb_analyse_intra: a namespace with i_satd_i16x16 / i8x8 / i4x4, i_predict16x16,
     i_predict8x8[4], i_predict4x4[16]"""
     a = types.SimpleNamespace(i_satd_i16x16=COST_MAX, i_satd_i8x8=COST_MAX, i_satd_i4x4=COST_MAX, i_predict16x16=0,
-                              i_predict8x8=[2] * 4, i_predict4x4=[2] * 16)
+                              i_predict8x8=[2] * 4, i_predict4x4=[2] * 16, x3=0)
     b_slice = cfg.slice_type == SLICE_B
     # I_16x16, :690-742
     predict_mode = I16x16_MODE_AVAILABLE[avail_idx(nb)]
@@ -302,10 +307,13 @@ def analyse_intra(bd, T, cfg, qp, lam, nb, nm, i_satd_inter, b_fast_intra, fenc,
             d[m] += lam * UE_SIZE[m]
             if d[m] < a.i_satd_i16x16:
                 a.i_satd_i16x16, a.i_predict16x16 = d[m], m
+        cnt["i16_x3_cost", mc._side(a.i_satd_i16x16, i16x16_thresh)] += 1
+        a.x3 = a.i_satd_i16x16
         if a.i_satd_i16x16 <= i16x16_thresh:
             mi.predict(bd, "16x16", 3, fdec, OY)
             p = orc.cmp(bd, "satd", PIXEL_16x16, fenc, 0, FENC, fdec, OY, FDEC) + lam * UE_SIZE[3]
             cnt["i16_plane_evaluated"] += 1
+            cnt["i16_plane_cost", mc._side(p, a.i_satd_i16x16)] += 1
             if p < a.i_satd_i16x16:
                 a.i_satd_i16x16, a.i_predict16x16 = p, 3
         else:
@@ -320,6 +328,7 @@ def analyse_intra(bd, T, cfg, qp, lam, nb, nm, i_satd_inter, b_fast_intra, fenc,
                 a.i_satd_i16x16, a.i_predict16x16 = i_satd, i_mode
     if b_slice:
         a.i_satd_i16x16 += lam * MB_B_COST["i16"]
+    cnt["i16_cost", mc._side(a.i_satd_i16x16, i16x16_thresh)] += 1
     if a.i_satd_i16x16 > i16x16_thresh:
         cnt["return_740"] += 1
         return a
@@ -337,6 +346,7 @@ def analyse_intra(bd, T, cfg, qp, lam, nb, nm, i_satd_inter, b_fast_intra, fenc,
             i_best, mode, edge = i8x8_block(bd, idx, n8, i_pred_mode, lam, fenc, fdec, cnt)
             a.i_predict8x8[idx] = mode
             i_cost += i_best + 3 * lam
+            cnt["i8_cost", mc._side(i_cost, i_satd_thresh), int(idx == 3)] += 1
             if idx == 3 or i_cost > i_satd_thresh:
                 break
             cache[4 * idx:4 * idx + 4] = [mode] * 4
@@ -348,6 +358,7 @@ def analyse_intra(bd, T, cfg, qp, lam, nb, nm, i_satd_inter, b_fast_intra, fenc,
         else:
             a.i_satd_i8x8 = COST_MAX
             i_cost = (i_cost * COST_DIV_FIX8[idx]) >> 8
+        cnt["i8_gate", mc._side(min(i_cost, a.i_satd_i16x16), (i_satd_inter * I8x8_THRESH[cfg.subme]) >> 2)] += 1
         if min(i_cost, a.i_satd_i16x16) > (i_satd_inter * I8x8_THRESH[cfg.subme]) >> 2:
             cnt["return_860"] += 1
             return a
@@ -369,8 +380,10 @@ def analyse_mb(bd, T, cf, cfg, qp, lam, nb, nm, satd_inter, b_fast_intra, fenc_y
     if cfg.slice_type == SLICE_I:
         a = analyse_intra(bd, T, cfg, qp, lam, nb, nm, COST_MAX, b_fast_intra, fenc_y, fdec_y, cnt)
         i_cost, kind = a.i_satd_i16x16, "i16"
+        cnt["type_i", "i4", mc._side(a.i_satd_i4x4, i_cost)] += 1
         if a.i_satd_i4x4 < i_cost:
             i_cost, kind = a.i_satd_i4x4, "i4"
+        cnt["type_i", "i8", mc._side(a.i_satd_i8x8, i_cost)] += 1
         if a.i_satd_i8x8 < i_cost:
             i_cost, kind = a.i_satd_i8x8, "i8"
         chroma_first = False
@@ -385,10 +398,13 @@ def analyse_mb(bd, T, cf, cfg, qp, lam, nb, nm, satd_inter, b_fast_intra, fenc_y
             a.i_satd_i4x4 += i_satd_chroma
         else:
             a = analyse_intra(bd, T, cfg, qp, lam, nb, nm, i_cost, b_fast_intra, fenc_y, fdec_y, cnt)
+        cnt["type_pb", "i16", mc._side(a.i_satd_i16x16, i_cost)] += 1
         if a.i_satd_i16x16 < i_cost:
             i_cost, kind = a.i_satd_i16x16, "i16"
+        cnt["type_pb", "i8", mc._side(a.i_satd_i8x8, i_cost)] += 1
         if a.i_satd_i8x8 < i_cost:
             i_cost, kind = a.i_satd_i8x8, "i8"
+        cnt["type_pb", "i4", mc._side(a.i_satd_i4x4, i_cost)] += 1
         if a.i_satd_i4x4 < i_cost:
             i_cost, kind = a.i_satd_i4x4, "i4"
     if kind is not None and not chroma_first:                        # analyse_update_cache
@@ -399,6 +415,7 @@ def analyse_mb(bd, T, cf, cfg, qp, lam, nb, nm, satd_inter, b_fast_intra, fenc_y
         modes = [a.i_predict8x8[i >> 2] for i in range(16)]
     else:
         modes = list(a.i_predict4x4)
+    cnt["x3_of_last_mb"] = a.x3                                      # for make_case's "x3/2" rule: a note, no count
     return kind, modes, cmode, (a.i_satd_i16x16, a.i_satd_i8x8, a.i_satd_i4x4, i_satd_chroma)
 
 
@@ -439,6 +456,7 @@ def encode(case, dec):
     out.mb_flags_out = case.flags.copy()
     out.cost = np.zeros((case.nmb, 4), np.int32)
     out.intra = np.zeros(case.nmb, bool)
+    out.x3 = [0] * case.nmb                                          # the I_16x16 cost before Plane (a list: no output)
     cnt = out.counters
     for mb in range(case.nmb):
         fl = int(case.flags[mb])
@@ -453,6 +471,7 @@ def encode(case, dec):
             kind, modes, cmode, cost = analyse_mb(bd, T, cf, case, qp, LAMBDA_TAB[qp], nb, nm, int(case.satd_inter[mb]),
                                                   bool(case.fast_intra[mb]), fenc_y, fdec_y, fenc_c, fdec_c, cnt)
             out.cost[mb] = cost
+            out.x3[mb] = cnt.pop("x3_of_last_mb")
             cnt["decided", case.slice_type, kind] += 1
             if kind is None:
                 continue
@@ -494,6 +513,7 @@ def expected(key, dec):
 # ------------------------------------------------------------------ inputs
 SHAPES = ((1, 1, 1), (3, 1, 1), (1, 3, 1), (2, 2, 1), (5, 4, 2), (7, 3, 3))     # (mb_width, mb_height, frames)
 FLAT_C, HGRAD, VGRAD, DIAG, STRIPES, TEX8, NOISE_C, KEEP = range(8)
+QUIET, QUIET_HEAD, QUIET_RAMP = -1, -2, -3                                           # the boundary pictures' own, see make_case
 
 
 def _content(rng, k, bd, h, w, qs):
@@ -527,14 +547,25 @@ def _content(rng, k, bd, h, w, qs):
 
 @functools.lru_cache(maxsize=None)
 def make_case(bd, cf, mbw, mbh, nframes, slice_type, cqm="flat", seed=0, b_i8x8=1, b_i4x4=1, b_chroma_me=0, subme=5,
-              content=None):
+              content=None, recipe=None):
     """mbintra_cases.make_case's inputs (an I picture: its all-intra case; P / B: its mixed case with
     the residual classes of mbenc_cases) plus: try_intra on most macroblocks, whose INTRA and type
     bits are cleared; fenc of two thirds of the try macroblocks replaced by a content class (flat,
     gradients, diagonal ramps, stripes, 8x8-structured texture, noise; a dither of up to a
     quantiser step); satd_inter drawn around the intra cost of a first pass that takes every
     macroblock as intra; fast_intra on a third of the P / B macroblocks.  content 'flat' /
-    'checker': one whole picture of it at qp 0 and QP_MAX_SPEC alternating."""
+    'checker': one whole picture of it at qp 0 and QP_MAX_SPEC alternating.
+    recipe (qp, class, amp, density, rule, offset): a boundary picture at one qp, "grey" being mid grey
+    + offset (with an offset the _128 predictions of a picture's first macroblock miss by a known
+    amount, which is what lets I_4x4's forty lambdas tie with I_16x16).  Class QUIET: grey with
+    single pixels of up to +-amp on density/16 of the positions; the costs are a few lambdas plus
+    a few small SATDs, so that they tie with each other.  QUIET_HEAD: mid grey with noise of +-density
+    inside the first `amp` 4x4 blocks only, so that the blocks after them cost nothing and a running
+    cost stays on a threshold it has reached.  QUIET_RAMP: grey + ((amp * x + density * y) >> 3) over
+    the picture with a speck of noise: Plane predicts it about as well as V / H / DC.  Otherwise a content class of _content, and satd_inter
+    is set from the first pass by `rule` to put a threshold of the reference on a cost: "c", "c+1",
+    "c-1" (the least intra cost), "i16/2" (2 * satd_inter = i_satd_i16x16, the fast-intra gate, with
+    fast_intra set), "x3/2" (the same with the cost before Plane is tried), "i8" ((5 * satd_inter) >> 2 = min(I_8x8, I_16x16), :858), "max" (nothing stops)."""
     base = mi.make_case(bd, cf, mbw, mbh, nframes, cqm, seed, slice_type == SLICE_I)
     rng = np.random.default_rng([bd, cf, mbw, mbh, nframes, slice_type, seed, 0xa11a])
     case = types.SimpleNamespace(**vars(base))
@@ -554,13 +585,34 @@ def make_case(bd, cf, mbw, mbh, nframes, slice_type, cqm="flat", seed=0, b_i8x8=
             t = False
         if n <= 4:
             t = not given if slice_type != SLICE_I else mb != 1 or n == 1
-        if content:
-            t = True
+        if content or (recipe and slice_type != SLICE_I):
+            t = not given if recipe else True
         try_intra[mb] = t
+        ys, cs, xs = slice(16 * my, 16 * my + 16), slice(crows * my, crows * my + crows), slice(16 * mx, 16 * mx + 16)
+        if recipe:                                                   # the given macroblocks too
+            q, klass, amp, density = recipe[:4]
+            qp[mb] = q
+            grey = (128 << (bd - 8)) + recipe[5]
+            quiet = lambda h, w: grey + rng.integers(-amp, amp + 1, (h, w)) * (rng.integers(0, 16, (h, w)) < density)
+            if klass == QUIET_HEAD:                                  # noise inside the first 4x4 blocks only
+                blk = np.full((16, 16), grey)
+                for idx in range(amp):
+                    bx, by = mi.block_xy(idx)
+                    blk[4 * by:4 * by + 3, 4 * bx:4 * bx + 3] += rng.integers(-density, density + 1, (3, 3))
+                fenc_y[f, ys, xs] = blk
+            elif klass == QUIET_RAMP:                                # a faint ramp across the picture and a speck of noise
+                yy, xx = np.mgrid[16 * my:16 * my + 16, 16 * mx:16 * mx + 16]
+                fenc_y[f, ys, xs] = grey + ((amp * xx + density * yy) >> 3) + rng.integers(-1, 2, (16, 16)) * (
+                    rng.integers(0, 16, (16, 16)) < 1)
+            else:
+                fenc_y[f, ys, xs] = quiet(16, 16) if klass == QUIET else _content(rng, klass, bd, 16, 16, 0.0)
+            if cf:
+                fenc_c[f, cs, xs] = quiet(crows, 16) if klass in (QUIET, QUIET_HEAD, QUIET_RAMP) else grey
         if not t:
             continue
         flags[mb] &= ~np.uint8(INTRA | T8 | I16 | mc.SKIP)
-        ys, cs, xs = slice(16 * my, 16 * my + 16), slice(crows * my, crows * my + crows), slice(16 * mx, 16 * mx + 16)
+        if recipe:
+            continue
         if content:
             qp[mb] = 0 if (mx + my + f) & 1 else mc.qp_max_spec(bd)
             yy, xx = np.mgrid[0:16, 0:16]
@@ -583,6 +635,8 @@ def make_case(bd, cf, mbw, mbh, nframes, slice_type, cqm="flat", seed=0, b_i8x8=
     case.satd_inter = np.zeros(n, np.int32)
     case.nmb = n
     case.key = (bd, cf, mbw, mbh, nframes, slice_type, cqm, seed, b_i8x8, b_i4x4, b_chroma_me, subme, content)
+    if recipe:
+        case.key += (recipe,)
     if slice_type != SLICE_I:
         # a first pass with every try macroblock taken as an I picture's gives the scale of its costs
         probe = types.SimpleNamespace(**vars(case))
@@ -595,6 +649,12 @@ def make_case(bd, cf, mbw, mbh, nframes, slice_type, cqm="flat", seed=0, b_i8x8=
                 c = int(min(first.cost[mb][:3]))
                 u = rng.random()
                 case.satd_inter[mb] = c if u < 0.1 else c + 1 if u < 0.2 else max(0, int(c * rng.uniform(0.3, 2.5)))
+                if recipe:
+                    i16, i8 = int(first.cost[mb][0]), int(first.cost[mb][1])
+                    rule = recipe[4]
+                    case.fast_intra[mb] = rule in ("i16/2", "x3/2")
+                    case.satd_inter[mb] = {"c": c, "c+1": c + 1, "c-1": max(0, c - 1), "i16/2": i16 >> 1, "x3/2": first.x3[mb] >> 1,
+                                           "i8": -(-4 * min(i8, i16) // 5), "max": COST_MAX - 1}[rule]
     return case
 
 
@@ -606,3 +666,83 @@ def case_keys(bd, cf, slice_type, **kw):
 def make_key(bd, cf, mbw, mbh, nframes, slice_type, cqm="flat", seed=0, b_i8x8=1, b_i4x4=1, b_chroma_me=0, subme=5,
              content=None):
     return (bd, cf, mbw, mbh, nframes, slice_type, cqm, seed, b_i8x8, b_i4x4, b_chroma_me, subme, content)
+
+
+# The boundary pictures: (what is pinned, the counter that says the picture is on the bound, the picture at
+# 8 bit, the picture at 10 bit), a picture being (chroma format, mbw, mbh, slice type, seed, options,
+# recipe).  On each, at its depth, the checker and the named comparison flipped at its boundary
+# (tests/mutants.py) give other bytes.  The costs depend on the reconstruction around a macroblock
+# and so on the depth's quantiser: where the 8-bit parameters miss the bound at 10 bit the 10-bit
+# picture has parameters of its own, found by the same search.
+def _p(cf, w, h, st, seed, recipe, **kw):
+    return (cf, w, h, st, seed, kw, recipe)
+
+
+BOUNDARY = (
+    ("I_8x8 loop entered with i_best = 0 (the guard is `i_best >= 0`, not `> 0`)", ("i8_best", "at"),
+     _p(0, 3, 2, 0, 753, (17, 3, 1, 2, "c-1", 0)), _p(1, 2, 2, 0, 446, (0, 2, 3, 2, "c-1", 0))),
+    ("chroma x3: two modes tie, the first evaluated stays", ("chroma_x3_cost", "at"),
+     _p(1, 2, 2, 0, 305, (20, -2, 5, 3, "c", 0), b_i8x8=0, b_chroma_me=1), _p(1, 3, 2, 1, 33, (20, -2, 7, 3, "max", 0), b_i8x8=0)),
+    ("chroma x3 tie at 4:2:2", ("chroma_x3_cost", "at"),
+     _p(2, 3, 2, 1, 377, (33, 6, 3, 4, "c-1", 0), b_i8x8=0), _p(2, 3, 2, 1, 593, (17, -2, 7, 2, "c+1", 0))),
+    ("chroma mode list: two modes tie", ("chroma_list_cost", "at"),
+     _p(1, 2, 2, 0, 924, (10, -1, 2, 2, "i16/2", 0)), _p(1, 3, 2, 1, 983, (17, -2, 7, 2, "c+1", 0))),
+    ("I_4x4 running cost = the threshold: goes on", ("i4_cost", "at", 0),
+     _p(0, 1, 1, 1, 525, (10, 1, 2, 8, "c", 0), b_i8x8=0), _p(0, 1, 1, 1, 525, (10, 1, 2, 8, "c", 0), b_i8x8=0)),
+    ("I_4x4 running cost = the threshold, 4:2:0", ("i4_cost", "at", 0),
+     _p(1, 2, 2, 1, 956, (20, 2, 0, 1, "c", 0), b_i8x8=0), _p(1, 2, 2, 1, 956, (20, 2, 0, 1, "c", 0), b_i8x8=0)),
+    ("i_satd_i16x16 = i16x16_thresh after I_16x16: not returned", ("i16_cost", "at"),
+     _p(0, 3, 2, 1, 795, (24, 1, 3, 4, "i16/2", 0)), _p(0, 3, 2, 1, 795, (24, 1, 3, 4, "i16/2", 0))),
+    ("i_satd_i16x16 = i16x16_thresh before Plane: Plane still evaluated", ("i16_x3_cost", "at"),
+     _p(0, 3, 2, 2, 470, (24, 6, 2, 1, "i16/2", 0)), _p(1, 3, 2, 2, 909, (0, -3, 5, -1, "x3/2", 0))),
+    ("i_satd_i16x16 = i16x16_thresh, one macroblock", ("i16_cost", "at"),
+     _p(0, 1, 1, 1, 329, (17, 2, 2, 2, "i16/2", 0), b_i8x8=0), _p(0, 1, 1, 1, 329, (17, 2, 2, 2, "i16/2", 0), b_i8x8=0)),
+    ("min(I_8x8, I_16x16) = the I8x8_THRESH bound: I_4x4 still tried", ("i8_gate", "at"),
+     _p(0, 1, 1, 1, 112, (17, 5, 1, 4, "i8", 0)), _p(1, 1, 1, 1, 31, (10, 5, 1, 2, "i8", 0))),
+    ("Plane cost = the best of V / H / DC: not taken", ("i16_plane_cost", "at"),
+     _p(0, 2, 2, 0, 81295, (17, -3, 0, 5, "max", 0)), _p(0, 3, 2, 0, 42954, (22, -3, 0, 3, "max", 0))),
+    ("I picture: I_4x4 cost = I_16x16 cost, I_16x16 stays", ("type_i", "i4", "at"),
+     _p(0, 1, 1, 0, 18581, (27, -2, 6, 2, "max", 3), b_i8x8=0), _p(0, 2, 1, 0, 59052, (27, -2, 15, 3, "max", 3), b_i8x8=0)),
+    ("I picture: I_8x8 cost = the least so far, which stays", ("type_i", "i8", "at"),
+     _p(1, 2, 2, 0, 337, (17, -1, 2, 8, "i16/2", 0)), _p(0, 3, 2, 0, 988, (20, -2, 8, 3, "i8", 0), b_chroma_me=1)),
+    ("I_8x8 running cost = the threshold: goes on", ("i8_cost", "at", 0),
+     _p(2, 2, 2, 0, 302, (17, -1, 1, 2, "max", 0)), _p(1, 3, 2, 0, 691, (10, -2, 4, 2, "max", 0))),
+)
+
+
+def boundary_key(bd, row):
+    cf, w, h, st, seed, kw, recipe = BOUNDARY[row][2 if bd == 8 else 3]
+    return make_key(bd, cf, w, h, 1, st, seed=seed, **kw) + (recipe,)
+
+
+def boundary_keys():
+    return [boundary_key(bd, row) for bd in (8, 10) for row in range(len(BOUNDARY))]
+
+
+OPTIONS = (dict(b_i8x8=0), dict(b_i4x4=0), dict(cqm="jvt"), dict(b_chroma_me=1), dict(subme=2))
+KEY_FIELDS = ("bd", "cf", "mbw", "mbh", "nframes", "slice_type", "cqm", "seed", "b_i8x8", "b_i4x4", "b_chroma_me", "subme",
+              "content")
+GPU_GROUPS = ("shapes", "options", "content", "noise", "boundary")
+
+
+def gpu_keys(group=None, **where):
+    """every (key, dec) tests/test_gpu_mbanalyse.py compares with the device byte for byte, which is
+    the list the boundary mutants of tests/test_cpu_mutants.py are held to.  group: one of GPU_GROUPS
+    (one test function each); where: fields of the key (KEY_FIELDS) or dec, the parametrised case."""
+    both = (8, 10)
+    keys = {"shapes": [(k, dec) for bd in both for cf in (0, 1, 2) for st in (0, 1, 2) for k in case_keys(bd, cf, st)
+                       for dec in (0, 1)],
+            "options": [(make_key(bd, cf, 5, 4, 2, st, **kw), 1) for bd in both for kw in OPTIONS
+                        for cf, st in ((1, 1), (1, 0), (2, 2))],
+            "content": [(make_key(bd, cf, w, h, 1, st, content=c), 1) for bd in both for c in ("flat", "checker")
+                        for cf, w, h, st in ((1, 5, 4, 0), (2, 3, 2, 1))],
+            "noise": [(make_key(bd, 1, 5, 4, 2, st), 1) for bd in both for st in (0, 1)],
+            "boundary": [(k, 1) for k in boundary_keys()]}
+    keys = [kd for g in GPU_GROUPS if group in (None, g) for kd in keys[g]]
+    pick = lambda kd, n: kd[1] if n == "dec" else kd[0][KEY_FIELDS.index(n)]
+    return [kd for kd in keys if all(pick(kd, n) == v for n, v in where.items())]
+
+
+def key_size(kd):
+    """macroblocks of a gpu_keys() entry: what its expected() costs"""
+    return kd[0][2] * kd[0][3] * kd[0][4]

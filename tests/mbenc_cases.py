@@ -101,6 +101,11 @@ def dct2x2dc(bd, d, dct4x4):
         dct4x4[k][0] = 0
 
 
+def _side(v, bound):
+    """for the branch counters: which side of a bound of the reference a value fell on"""
+    return "below" if v < bound else "above" if v > bound else "at"
+
+
 def _bits(mask, n):
     return [i for i in range(n) if (mask >> i) & 1]
 
@@ -137,6 +142,7 @@ def encode_luma(bd, T, dec, t8, qp, fenc, fdec, o, cnt):
                 f("zigzag_scan_8x8")(0, A(lev), A(dct8[idx]))
                 if dec:
                     s = f("decimate_score64")(A(lev))
+                    cnt["score8x8", _side(s, 4)] += 1
                     i_decimate_mb += s
                     if s >= 4:
                         plane_cbp |= 1 << idx
@@ -144,6 +150,8 @@ def encode_luma(bd, T, dec, t8, qp, fenc, fdec, o, cnt):
                         part += 1
                 else:
                     plane_cbp |= 1 << idx
+        if dec and nzs:
+            cnt["score_mb", _side(i_decimate_mb, 6)] += 1
         if i_decimate_mb >= 6 or not dec:
             o.cbp_luma |= plane_cbp
             for idx in _bits(plane_cbp, 4):
@@ -171,11 +179,15 @@ def encode_luma(bd, T, dec, t8, qp, fenc, fdec, o, cnt):
                         i_decimate_8x8 += f("decimate_score16")(A(o.level[idx]))
                     o.nnz[idx] = 1
                 i_decimate_mb += i_decimate_8x8
+                if dec:
+                    cnt["score8x8", _side(i_decimate_8x8, 4)] += 1
                 if i_decimate_8x8 < 4:
                     o.nnz[4 * i8:4 * i8 + 4] = 0
                     part += 1
                 else:
                     plane_cbp |= 1 << i8
+        if dec and nzs:
+            cnt["score_mb", _side(i_decimate_mb, 6)] += 1
         if i_decimate_mb < 6:
             plane_cbp = 0
             o.nnz[:16] = 0
@@ -191,6 +203,7 @@ def encode_luma(bd, T, dec, t8, qp, fenc, fdec, o, cnt):
 def mb_optimize_chroma_dc(bd, dct_dc, dequant_mf, qp, c422, cnt):
     """macroblock.c:245-257"""
     dmf = int(dequant_mf[qp % 6][0]) << (qp // 6)
+    cnt["dmf", _side(dmf, 32 * 64)] += 1
     if dmf > 32 * 64:
         cnt["dmf_shortcut"] += 1
         return 1
@@ -228,11 +241,16 @@ def encode_chroma(bd, T, dec, c422, qp, fenc, fdec, o, cnt):
         for i in range(c422 + 1):
             f("add8x8_idct_dc")(A(fdec, p_dst + 8 * i * FDEC), A(dct_dc, 4 * i))
 
+    if dec:
+        cnt["chroma_qp", _side(qp, 18)] += 1
     if dec and qp >= 18:
         thresh = (LAMBDA2[qp] + 16) >> 5 if c422 else (LAMBDA2[qp] + 32) >> 6
         ssd = np.zeros(2, np.int32)
-        if f("var2")(PIXEL_8x16 if c422 else PIXEL_8x8, A(fenc), A(fdec), A(ssd)) < thresh * 4:
+        score = f("var2")(PIXEL_8x16 if c422 else PIXEL_8x8, A(fenc), A(fdec), A(ssd))
+        cnt["var2", _side(score, thresh * 4)] += 1
+        if score < thresh * 4:
             for ch in range(2):
+                cnt["ssd", _side(ssd[ch], thresh)] += 1
                 if ssd[ch] > thresh:
                     p_src, p_dst = 8 * ch, 16 * ch
                     dct_dc[:] = 0
@@ -271,6 +289,8 @@ def encode_chroma(bd, T, dec, c422, qp, fenc, fdec, o, cnt):
                 o.nnz[idx] = 1
         nz_dc = quant_dc()
         o.nnz_dc[ch] = int(nz_dc != 0)
+        if dec and nz_ac:
+            cnt["score_chroma", _side(i_decimate_score, 7)] += 1
         if i_decimate_score < 7 or not nz_ac:
             o.nnz[16 + 16 * ch:32 + 16 * ch] = 0
             if not nz_dc:
@@ -473,14 +493,62 @@ def _qstep(qp):
     return 0.625 * 2.0 ** (qp / 6.0)
 
 
+H4 = np.array([[1, 1, 1, 1], [2, 1, -1, -2], [1, -1, -1, 1], [1, -2, 2, -1]])        # the 4x4 core transform's rows
+
+
+def _boundary_case(bd, cf, mbw, mbh, nframes, cqm, recipe, key):
+    """one macroblock per entry (qp, mb_flags, rects, waves) of `recipe`: mid-grey fenc, pred = fenc +
+    the rectangles (plane 0 / 1 / 2 = Y / U / V, y, x, h, w, amplitude) + the waves (plane, y, x, u, v,
+    c: c * outer(H4[u], H4[v]) on the 4x4 block at y, x), added up.  A few flat patches and basis
+    functions of a small whole amplitude quantise to a handful of +-1 levels, whose decimate scores
+    add up to the small totals the reference compares with 4, 6 and 7, and put the chroma var2 / ssd
+    exactly on the thresholds of the early-out.  BOUNDARY names what each entry pins."""
+    n = nframes * mbw * mbh
+    assert n == len(recipe)
+    crows = {0: 0, 1: 8, 2: 16}[cf]
+    grey = 128 << (bd - 8)
+    res_y = np.zeros((nframes, 16 * mbh, 16 * mbw), np.int64)
+    res_c = np.zeros((nframes, crows * mbh, 16 * mbw), np.int64)
+    for mb, (q, fl, rects, waves) in enumerate(recipe):
+        f, r = divmod(mb, mbw * mbh)
+        my, mx = divmod(r, mbw)
+        mb_y = res_y[f, 16 * my:16 * my + 16, 16 * mx:16 * mx + 16]
+        mb_c = res_c[f, crows * my:crows * my + crows, 16 * mx:16 * mx + 16]
+        planes = (mb_y, mb_c[:, 0::2], mb_c[:, 1::2])
+        for plane, y, x, h, w, a in rects:
+            if plane == 0 or cf:
+                assert y + h <= planes[plane].shape[0] and x + w <= planes[plane].shape[1]
+                planes[plane][y:y + h, x:x + w] += a
+        for plane, y, x, u, v, c in waves:
+            if plane == 0 or cf:
+                assert y + 4 <= planes[plane].shape[0] and x + 4 <= planes[plane].shape[1]
+                planes[plane][y:y + 4, x:x + 4] += c * np.outer(H4[u], H4[v])
+    fenc_y, pred_y = np.full_like(res_y, grey), grey + res_y
+    fenc_c, pred_c = (np.full_like(res_c, grey), grey + res_c) if cf else (None, None)
+    pdt = orc.pixel_dtype(bd)
+    pm = (1 << bd) - 1
+    assert 0 <= pred_y.min() and pred_y.max() <= pm and (not cf or (0 <= pred_c.min() and pred_c.max() <= pm))
+    return types.SimpleNamespace(
+        bd=bd, cf=cf, mbw=mbw, mbh=mbh, nframes=nframes, nmb=n, cqm=cqm, chroma_rows=crows,
+        fenc_y=fenc_y.astype(pdt), pred_y=pred_y.astype(pdt), fenc_c=fenc_c.astype(pdt) if cf else None,
+        pred_c=pred_c.astype(pdt) if cf else None, qp=np.array([r[0] for r in recipe], np.int8),
+        flags=np.array([r[1] for r in recipe], np.uint8), klass=np.full(n, -1, np.int32), qp_table=chroma_qp_table(bd),
+        key=key)
+
+
 @functools.lru_cache(maxsize=None)
-def make_case(bd, cf, mbw, mbh, nframes, cqm="flat", seed=0):
-    """Seeded inputs.  fenc is synthetic texture; pred = fenc + a per-macroblock residual class:
+def make_case(bd, cf, mbw, mbh, nframes, cqm="flat", seed=0, recipe=None):
+    """recipe "boundary": the boundary macroblocks of BOUNDARY (or a recipe itself), see
+    _boundary_case.  Otherwise:
+    Seeded inputs.  fenc is synthetic texture; pred = fenc + a per-macroblock residual class:
     zero; one isolated bump of +-1..2 quantiser steps; noise scaled to the macroblock's qp; noise
     with a strength per 8x8 quadrant (nothing / a faint flat patch / strong), which is what takes
     the per-8x8 and per-macroblock decimation apart; a flat chroma offset; a +-1 chroma DC at low
     qp; a full-scale 0 / max checker at qp 0 and at qp_max_spec.  qp varies per macroblock over
     0..qp_max_spec; mb_flags mixes transform 4 / 8, D_16x16, skip and intra."""
+    if recipe is not None:
+        return _boundary_case(bd, cf, mbw, mbh, nframes, cqm, boundary_recipe(cf, cqm)[2] if recipe == "boundary" else recipe,
+                              (bd, cf, mbw, mbh, nframes, cqm, seed, recipe))
     rng = np.random.default_rng([bd, cf, mbw, mbh, nframes, seed, 264])
     pm, qmax = (1 << bd) - 1, qp_max_spec(bd)
     scale = 1 << (bd - 8)
@@ -578,3 +646,81 @@ def make_case(bd, cf, mbw, mbh, nframes, cqm="flat", seed=0):
 def case_keys(bd, cf):
     """the case list of one (bit depth, chroma format): every shape with the flat matrices"""
     return [(bd, cf, w, h, n, "flat", 0) for w, h, n in SHAPES]
+
+
+# The boundary macroblocks: (what is pinned, chroma formats, (qp, mb_flags, rects, waves)).  Each puts one
+# comparison of the reference exactly on its bound (the counters of encode() say so, and
+# tests/test_cpu_mbenc.py asserts it); the flipped comparison (tests/mutants.py) gives other bytes on
+# the ones marked *.  They were found by search over a few rectangles and waves per macroblock.
+_U422 = (1, 0, 0, 16, 8)
+_RAMP420 = ((1, 4, 4, 4, 1, 2), (1, 4, 7, 4, 1, -2), (1, 4, 5, 1, 2, 3), (1, 5, 5, 1, 2, 1), (1, 6, 5, 1, 2, -2), (1, 7, 5, 1, 2, -4),
+            (1, 4, 5, 4, 1, 1))
+# (with the flat matrices no 4:2:0 plane whose ssd is at most thresh has a DC that quantises to a level, at any
+# chroma qp from 18 up: the least ssd for one, sum^2 / 64, is above thresh.  The JVT matrices quantise the DC finer.)
+BOUNDARY = (
+    ("8x8 transform, decimate_score64 of a block = 4 *", (0, 1, 2), (22, T8, ((0, 4, 0, 4, 4, 9),), ((0, 8, 0, 2, 0, 4),))),
+    ("8x8 transform, macroblock score = 6 *", (0, 1, 2), (17, T8, ((0, 8, 12, 4, 4, 2),), ())),
+    ("8x8 transform, macroblock score = 6 at qp 30 *", (0, 1, 2), (30, T8, (), ((0, 0, 12, 2, 1, 9),))),
+    ("4x4 transform, score of an 8x8 = 4 *", (0, 1, 2), (17, 0, ((0, 4, 12, 4, 4, 2),), ((0, 4, 8, 0, 2, -1), (0, 0, 0, 1, 0, 3)))),
+    ("4x4 transform, macroblock score = 6 *", (0, 1, 2), (17, 0, ((0, 4, 0, 4, 4, -2),), ((0, 0, 12, 0, 2, -1), (0, 0, 0, 0, 1, 1)))),
+    ("chroma score = 7 at 4:2:0 *", (1,), (22, 0, (), ((1, 4, 0, 0, 1, 2), (1, 4, 4, 2, 0, -3), (1, 0, 4, 2, 0, 3)))),
+    ("chroma score = 7 at 4:2:2 *", (2,), (19, 0, (), ((1, 4, 4, 2, 0, -2), (1, 4, 4, 0, 1, -1), (1, 4, 0, 2, 0, -2)))),
+    ("chroma qp 17: no early-out", (1, 2), (17, 0, (), ((1, 0, 4, 1, 1, -1),))),
+    ("chroma qp = 18: the early-out drops what the full path codes *", (1, 2), (18, 0, (), ((1, 0, 4, 1, 1, -1),))),
+    ("chroma qp 19", (1, 2), (19, 0, (), ((1, 0, 4, 1, 1, -1),))),
+    ("var2 = 4 * thresh = 92 at 4:2:0, qp 20: two flat columns round a ramp *", (1,), (20, 0, _RAMP420, ())),
+    ("ssd of U = thresh = 36 at 4:2:0, qp 22, JVT matrices: a DC the early-out must not code *", (1,),
+     (22, 0, tuple((1, 4 * (b >> 1), 4 * (b & 1), 3, 3, 1) for b in range(4)), ()), "jvt"),
+    ("var2 = 4 * thresh at 4:2:2, qp 18 *", (2,), (18, 0, (), ((1, 0, 4, 1, 1, 1), (1, 0, 0, 2, 0, 1)))),
+    ("ssd of U = thresh at 4:2:2, qp 25: a DC the early-out must not code *", (2,),
+     (25, 0, (_U422 + (1,), (1, 0, 2, 1, 1, -1), (1, 2, 7, 1, 1, 3), (1, 5, 2, 1, 1, 1)), ())),
+    ("chroma DC dmf 1792 < 32 * 64 at 4:2:2 (qp 18 + 3)", (2,), (18, 0, (_U422 + (-1,),), ())),
+    ("chroma DC dmf = 32 * 64 at 4:2:2 (qp 19 + 3): optimised *", (2,), (19, 0, (_U422 + (-1,),), ())),
+    ("chroma DC dmf 2304 at 4:2:2 (qp 20 + 3): not optimised", (2,), (20, 0, (_U422 + (-1,),), ())),
+    ("chroma DC dmf = 32 * 64 at 4:2:0 (qp 22)", (1,), (22, 0, ((1, 0, 0, 8, 8, -2),), ())),
+)
+
+
+def boundary_recipe(cf, cqm="flat"):
+    """the boundary macroblocks of chroma format cf and the matrices cqm as one picture: (mbw, mbh,
+    recipe, names)"""
+    rows = [(b[0], b[2]) for b in BOUNDARY if cf in b[1] and (b[3:] or ("flat",))[0] == cqm]
+    mbw = min(5, len(rows))
+    mbh = -(-len(rows) // mbw)
+    rows += [("filler", (26, 0, (), ()))] * (mbw * mbh - len(rows))
+    return mbw, mbh, tuple(e for _, e in rows), [n for n, _ in rows]
+
+
+def boundary_keys():
+    """one picture per (bit depth, chroma format); at 10 bit the same residuals at the same qp meet
+    the same quantiser (the tables hold QP_BD_OFFSET), with pixels two bits wider"""
+    keys = []
+    for bd in (8, 10):
+        for cf, cqm in ((0, "flat"), (1, "flat"), (2, "flat"), (1, "jvt")):
+            mbw, mbh, _, _ = boundary_recipe(cf, cqm)
+            keys.append((bd, cf, mbw, mbh, 1, cqm, 0, "boundary"))
+    return keys
+
+
+def jvt_keys():
+    return [(bd, cf, 5, 4, 2, "jvt", 0) for bd in (8, 10) for cf in (1, 2)]
+
+
+GPU_GROUPS = ("shapes", "jvt", "boundary")
+
+
+def gpu_keys(group=None, **where):
+    """every (key, dec) tests/test_gpu_mbenc.py compares with the device byte for byte, which is the
+    list the boundary mutants of tests/test_cpu_mutants.py are held to.  group: one of GPU_GROUPS
+    (one test function each); where: bd / cf / dec of one parametrised case of that function."""
+    keys = {"shapes": [(k, dec) for bd in (8, 10) for cf in (0, 1, 2) for dec in (0, 1) for k in case_keys(bd, cf)],
+            "jvt": [(k, 1) for k in jvt_keys()],
+            "boundary": [(k, 1) for k in boundary_keys()]}
+    keys = [kd for g in GPU_GROUPS if group in (None, g) for kd in keys[g]]
+    pick = {"bd": lambda kd: kd[0][0], "cf": lambda kd: kd[0][1], "dec": lambda kd: kd[1]}
+    return [kd for kd in keys if all(pick[n](kd) == v for n, v in where.items())]
+
+
+def key_size(kd):
+    """macroblocks of a gpu_keys() entry: what its expected() costs"""
+    return kd[0][2] * kd[0][3] * kd[0][4]

@@ -251,6 +251,8 @@ def encode_i16x16(bd, T, dec, qp, mode, fenc, fdec, o, cnt):
                 if decimate_score < 6:
                     decimate_score += f("decimate_score15")(A(o.level[idx]))
                 o.nnz[idx] = 1
+    if dec and block_cbp:
+        cnt["i16_score", mc._side(decimate_score, 6)] += 1
     if decimate_score < 6:
         if block_cbp:
             cnt["i16_decimated"] += 1
@@ -626,15 +628,34 @@ def valid_modes(kind, n):
     return [m for m, v in ok.items() if v]
 
 
+def _boundary_case(bd, cf, mbw, mbh, nframes, cqm, recipe, key):
+    """one I_16x16 / DC_128 macroblock per entry (qp, rects, waves) of `recipe`, chroma DC_128: the
+    prediction is mid grey whatever the neighbours, fenc = mid grey + mbenc_cases' rectangles and
+    waves, so the residual and with it the AC decimate score is the recipe's alone"""
+    base = mc._boundary_case(bd, cf, mbw, mbh, nframes, cqm, tuple((q, 0, r, w) for q, r, w in recipe), key)
+    case = types.SimpleNamespace(**vars(base))
+    case.fenc_y, case.fenc_c = base.pred_y, base.pred_c            # grey + the residual
+    case.pred_y, case.pred_c = base.fenc_y, base.fenc_c            # what an inter call would start from: unused
+    case.flags = np.full(base.nmb, INTRA | I16, np.uint8)
+    case.pred_mode = np.zeros((base.nmb, 16), np.int8)
+    case.pred_mode[:, 0] = 6
+    case.chroma_pred_mode = np.full(base.nmb, 6, np.int8)
+    case.all_intra = True
+    return case
+
+
 @functools.lru_cache(maxsize=None)
-def make_case(bd, cf, mbw, mbh, nframes, cqm="flat", seed=0, all_intra=False):
+def make_case(bd, cf, mbw, mbh, nframes, cqm="flat", seed=0, all_intra=False, recipe=None):
     """mbenc_cases.make_case's inputs (same fenc, prediction, qp and flags, its INTRA macroblocks;
     all_intra: every macroblock INTRA, no skip; only the qp of a third of the intra macroblocks is
-    redrawn, see below) plus the type of each intra macroblock (I_4x4,
+    redrawn, see below; recipe: the boundary picture, see _boundary_case) plus the type of each intra macroblock (I_4x4,
     I_8x8 through T8, I_16x16 through bit 4) and its modes, drawn from the modes valid at its
     position.  A full-scale checker macroblock at qp_max_spec becomes I_16x16 / DC_128: its DC
     quantises to nothing while its AC does not, the one arm of mb_encode_i16x16 noise does not
     reach."""
+    if recipe is not None:
+        return _boundary_case(bd, cf, mbw, mbh, nframes, cqm, BOUNDARY_RECIPE if recipe == "boundary" else recipe,
+                              (bd, cf, mbw, mbh, nframes, cqm, seed, all_intra, recipe))
     base = mc.make_case(bd, cf, mbw, mbh, nframes, cqm, seed)
     rng = np.random.default_rng([bd, cf, mbw, mbh, nframes, seed, int(all_intra), 2640])
     case = types.SimpleNamespace(**vars(base))
@@ -712,3 +733,45 @@ def all_intra_key(bd, cf):
     """the I picture of tests/test_gpu_mbintra.py"""
     w, h, n, ai = ALL_INTRA_PICTURE
     return (bd, cf, w, h, n, "flat", 0, ai)
+
+
+def jvt_keys():
+    return [(bd, cf, 5, 4, 2, "jvt", 0, False) for bd in (8, 10) for cf in (1, 2)]
+
+
+# The boundary macroblocks, (what is pinned, (qp, rects, waves)): the AC decimate score of
+# mb_encode_i16x16 (macroblock.c:214) just below, exactly at and above 6.  On the ones marked * the
+# flipped comparison (tests/mutants.py) gives other bytes.  Found by search over one or two waves.
+BOUNDARY = (
+    ("I_16x16 AC score 3 < 6: decimated", (28, (), ((0, 8, 8, 1, 1, -2),))),
+    ("I_16x16 AC score = 6: kept *", (28, (), ((0, 4, 12, 0, 1, -3), (0, 8, 12, 0, 1, -2)))),
+    ("I_16x16 AC score > 6", (28, (), ((0, 8, 4, 1, 0, 10),))),
+    ("I_16x16 AC score = 6 at qp 36 *", (36, (), ((0, 0, 4, 0, 1, 5), (0, 12, 8, 0, 1, 9)))),
+)
+BOUNDARY_RECIPE = tuple(e for _, e in BOUNDARY)
+
+
+def boundary_keys():
+    """the boundary macroblocks as a 2x2 picture per (bit depth, chroma format)"""
+    return [(bd, cf, 2, 2, 1, "flat", 0, True, "boundary") for bd in (8, 10) for cf in (0, 1, 2)]
+
+
+GPU_GROUPS = ("shapes", "jvt", "all_intra", "boundary")
+
+
+def gpu_keys(group=None, **where):
+    """every (key, dec) tests/test_gpu_mbintra.py compares with the device byte for byte, which is
+    the list the boundary mutants of tests/test_cpu_mutants.py are held to.  group: one of GPU_GROUPS
+    (one test function each); where: bd / cf / dec of one parametrised case of that function."""
+    keys = {"shapes": [(k, dec) for bd in (8, 10) for cf in (0, 1, 2) for dec in (0, 1) for k in case_keys(bd, cf)],
+            "jvt": [(k, 1) for k in jvt_keys()],
+            "all_intra": [(all_intra_key(bd, cf), dec) for bd in (8, 10) for cf in (0, 1, 2) for dec in (1, 0)],
+            "boundary": [(k, 1) for k in boundary_keys()]}
+    keys = [kd for g in GPU_GROUPS if group in (None, g) for kd in keys[g]]
+    pick = {"bd": lambda kd: kd[0][0], "cf": lambda kd: kd[0][1], "dec": lambda kd: kd[1]}
+    return [kd for kd in keys if all(pick[n](kd) == v for n, v in where.items())]
+
+
+def key_size(kd):
+    """macroblocks of a gpu_keys() entry: what its expected() costs"""
+    return kd[0][2] * kd[0][3] * kd[0][4]

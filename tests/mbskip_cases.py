@@ -341,8 +341,29 @@ _MIX = {False: [ZERO, ZERO, FAINT, FAINT, FAINT, BUMP, MED, MED, NOISE, NOISE, C
                CAC, CBUMP, CHECKER]}
 
 
+def _boundary_case(bd, cf, mbw, mbh, nframes, cqm, recipe, key):
+    """leg "b" (the prediction handed over as planes) on mbenc_cases' boundary macroblocks: one per
+    entry (qp, rects, waves) of `recipe`, fenc mid grey, prediction = fenc + the rectangles and waves"""
+    base = mbc._boundary_case(bd, cf, mbw, mbh, nframes, cqm, tuple((q, 0, r, w) for q, r, w in recipe), key)
+    n, crows = base.nmb, base.chroma_rows
+
+    def blocks(plane, h, w):
+        return plane.reshape(nframes, mbh, h, mbw, w).transpose(0, 1, 3, 2, 4).reshape(n, h, w).astype(np.int64)
+    fy, py = blocks(base.fenc_y, 16, 16), blocks(base.pred_y, 16, 16)
+    fu = fv = pu = pv = None
+    if cf:
+        fc, pc = blocks(base.fenc_c, crows, 16), blocks(base.pred_c, crows, 16)
+        fu, fv, pu, pv = fc[..., 0::2], fc[..., 1::2], pc[..., 0::2], pc[..., 1::2]
+    qp_table = mbc.chroma_qp_table(bd)
+    return types.SimpleNamespace(
+        bd=bd, cf=cf, mbw=mbw, mbh=mbh, nframes=nframes, nmb=n, leg="b", cqm=cqm, W=16 * mbw, H=16 * mbh, crows=crows,
+        qp=base.qp, qpc=qp_table[base.qp].astype(np.int64), qp_table=qp_table, klass=np.full(n, -1), pskip_mv=np.zeros((n, 2), np.int16),
+        weights=(None, None, None), ref=None, blocks=types.SimpleNamespace(fenc=(fy, fu, fv), pred=(py, pu, pv)),
+        fenc=[base.fenc_y] + ([base.fenc_c] if cf else []), pred=[base.pred_y] + ([base.pred_c] if cf else []), key=key)
+
+
 @functools.lru_cache(maxsize=None)
-def make_case(bd, cf, mbw, mbh, nframes, leg, cqm="flat", seed=0):
+def make_case(bd, cf, mbw, mbh, nframes, leg, cqm="flat", seed=0, recipe=None):
     """Seeded inputs of one probe.  The reference is synthetic texture; each macroblock has a skip
     vector (zero, small, or anywhere inside its limits; at the four corner macroblocks of every
     frame beyond mv_max / below mv_min, so the clip acts) and fenc = its prediction at that vector
@@ -351,7 +372,11 @@ def make_case(bd, cf, mbw, mbh, nframes, leg, cqm="flat", seed=0):
     quantiser step; chroma noise around thresh and 4 * thresh; a flat chroma offset (the DC
     check); a zero-sum chroma pattern per 4x4 block (the AC check alone); a +-1 chroma pixel at low
     qp; a full-scale 0 / max checker against its inverse in the reference at qp 0 and qp_max_spec.
-    leg "pw" weights all three planes; leg "b" hands the same prediction over as planes."""
+    leg "pw" weights all three planes; leg "b" hands the same prediction over as planes.
+    recipe: the boundary picture, see _boundary_case."""
+    if recipe is not None:
+        return _boundary_case(bd, cf, mbw, mbh, nframes, cqm, boundary_recipe(cf, cqm) if recipe == "boundary" else recipe,
+                              (bd, cf, mbw, mbh, nframes, leg, cqm, seed, recipe))
     rng = np.random.default_rng([bd, cf, mbw, mbh, nframes, LEGS.index(leg), cqm == "jvt", seed, 985])
     pm, qmax = (1 << bd) - 1, mbc.qp_max_spec(bd)
     n = nframes * mbw * mbh
@@ -580,3 +605,64 @@ def make_convert_case(mbw, mbh, nframes, b_bframe, seed=0):
     ps = pskip_mv(mv0, ref0, mbw, mbh)
     return types.SimpleNamespace(mbw=mbw, mbh=mbh, nframes=nframes, nmb=n, b_bframe=b_bframe, flags=flags, cbp=cbp,
                                  mv0=mv0, ref0=ref0, pskip=ps, direct=direct)
+
+
+# ------------------------------------------------------------------ what the GPU tests compare
+# The boundary macroblocks of the probe: (what is pinned, chroma formats, (qp, rects, waves)), residuals of
+# tests/mbenc_cases.py's kind.  On the ones marked * the comparison flipped at its boundary
+# (tests/mutants.py) gives the other answer.
+_U422 = (1, 0, 0, 16, 8)
+BOUNDARY = (
+    ("luma score 3 < 6: skip", (0, 1, 2), (17, ((0, 4, 0, 4, 4, -2),), ())),
+    ("luma score = 6: no skip *", (0, 1, 2), (17, ((0, 4, 0, 4, 4, -2),), ((0, 0, 12, 0, 2, -1), (0, 0, 0, 0, 1, 1)))),
+    ("chroma AC score = 7 at 4:2:0: no skip *", (1,), (22, (), ((1, 4, 0, 0, 1, 2), (1, 4, 4, 2, 0, -3), (1, 0, 4, 2, 0, 3)))),
+    ("chroma AC score = 7 at 4:2:2: no skip *", (2,), (19, (), ((1, 4, 4, 2, 0, -2), (1, 4, 4, 0, 1, -1), (1, 4, 0, 2, 0, -2)))),
+    ("ssd of U = thresh at 4:2:2 with a DC that quantises to a level: no skip *", (2,),
+     (25, (_U422 + (1,), (1, 0, 2, 1, 1, -1), (1, 2, 7, 1, 1, 3), (1, 5, 2, 1, 1, 1)), ())),
+    ("ssd of U = thresh = 36 at 4:2:0, qp 22, JVT matrices (the flat ones leave such a DC 0): no skip *", (1,),
+     (22, tuple((1, 4 * (b >> 1), 4 * (b & 1), 3, 3, 1) for b in range(4)), ()), "jvt"),
+)
+GPU_GROUPS = ("pskip", "probe", "convert", "boundary")
+
+
+def boundary_recipe(cf, cqm="flat"):
+    return tuple(b[2] for b in BOUNDARY if cf in b[1] and (b[3:] or ("flat",))[0] == cqm)
+
+
+def boundary_keys():
+    """one row of boundary macroblocks per (bit depth, chroma format), on leg b"""
+    return [(bd, cf, len(boundary_recipe(cf, cqm)), 1, 1, "b", cqm, 0, "boundary")
+            for bd in (8, 10) for cf, cqm in ((0, "flat"), (1, "flat"), (2, "flat"), (1, "jvt"))]
+
+
+def gpu_keys(group=None, **where):
+    """every entry tests/test_gpu_mbskip.py compares with the device value for value, which is the
+    list the boundary mutants of tests/test_cpu_mutants.py are held to: ("pskip", (mbw, mbh, nf),
+    seed) for mb_predict_mv_pskip, ("probe", key) for mb_probe_skip, ("convert", (mbw, mbh, nf),
+    b_bframe) for mb_skip_convert.  group: one of GPU_GROUPS (one test function each); where: bd /
+    cf / leg of a probe key, shape or bframe of the other entries."""
+    keys = {"pskip": [("pskip", sh, seed) for sh in SHAPES for seed in (0, 1)],
+            "probe": [("probe", k) for bd in (8, 10) for cf in (0, 1, 2, 3) for leg in LEGS for k in case_keys(bd, cf, leg)],
+            "convert": [("convert", sh, bf) for bf in (0, 1) for sh in SHAPES],
+            "boundary": [("probe", k) for k in boundary_keys()]}
+    keys = [e for g in GPU_GROUPS if group in (None, g) for e in keys[g]]
+    pick = {"bd": lambda e: e[1][0], "cf": lambda e: e[1][1], "leg": lambda e: e[1][5], "shape": lambda e: e[1],
+            "bframe": lambda e: e[2]}
+    return [e for e in keys if all(pick[n](e) == v for n, v in where.items())]
+
+
+def gpu_expected(entry):
+    """what the device's output of a gpu_keys() entry is compared with"""
+    if entry[0] == "pskip":
+        mv0, ref0 = make_field(*entry[1], entry[2])
+        return pskip_mv(mv0, ref0, entry[1][0], entry[1][1])
+    if entry[0] == "probe":
+        return expected(entry[1])[0]
+    c = make_convert_case(*entry[1], entry[2])
+    return skip_convert(c.flags, c.cbp, c.mv0, c.ref0, c.pskip, entry[2], c.direct, c.mbw, c.mbh)
+
+
+def key_size(entry):
+    """macroblocks of a gpu_keys() entry: what it costs"""
+    k = entry[1]
+    return k[2] * k[3] * k[4] if entry[0] == "probe" else k[0] * k[1] * k[2] // 8 + 1

@@ -432,3 +432,36 @@ def test_deblock_entries_return_enodev_without_device():
         for cf in range(4):
             assert getattr(L, f"x264hip_{bd}_deblock_frames")(ctypes.byref(_d(x, cf=cf)), 5, 4, 2, None) == ENODEV
     assert L.x264hip_deblock_strength(ctypes.byref(_s(x)), 5, 4, 2, BS, None) == ENODEV
+
+
+# ------------------------------------------------------------------ the boundary pictures
+@pytest.mark.parametrize("bd", [8, 10])
+def test_boundary_pictures_alone_meet_every_line_filter_bound(bd):
+    """at each depth the pictures of deblock_cases.BOUNDARY by themselves tell every alpha / beta /
+    tc0 comparison of the four line filters, flipped at its boundary (tests/mutants.py), from the
+    checker: each bound is met exactly, and the step either side of it is filtered differently"""
+    import mutants as mu
+    keys = [k for k in dc.boundary_keys() if k[0] == bd]
+    assert keys and all(k[2] * k[3] * k[4] <= 40 for k in keys)
+    filters = ("edge_luma", "edge_chroma", "edge_luma_intra", "edge_chroma_intra")
+    sites = [s for s in mu.sites("deblock_cases") if s.func in filters and s.text != "tc > 0"]
+    assert len(sites) == 18
+    for s in sites:
+        m = mu.load("deblock_cases", s.index)
+        assert any(mu.differs(m.expected(k), dc.expected(k)) for k in keys), (bd, s.func, s.text)
+
+
+def test_boundary_fields_meet_the_vector_limits():
+    import mutants as mu
+    for s in mu.sites("deblock_cases"):
+        if s.func == "deblock_strength_py":
+            m = mu.load("deblock_cases", s.index)
+            entries = dc.gpu_keys("boundary")
+            assert any(e[0] == "strength" and mu.differs(m.gpu_expected(e), dc.gpu_expected(e)) for e in entries), s.text
+
+
+def test_gpu_keys_are_the_groups_of_the_gpu_tests():
+    """the parametrised lists of tests/test_gpu_deblock.py add up to gpu_keys(), nothing twice"""
+    picked = [e for g in dc.GPU_GROUPS for e in dc.gpu_keys(g)]
+    assert picked == dc.gpu_keys() and len(set(picked)) == len(picked)
+    assert {e[1] for e in dc.gpu_keys() if e[0] == "frames"} >= set(dc.ALL)

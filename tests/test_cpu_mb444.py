@@ -77,7 +77,8 @@ def test_each_plane_alone_without_carry_is_encode_luma(bd, dec):
             assert np.array_equal(o1.level[:16][o1.nnz[:16] != 0], o2.level[:16][o2.nnz[:16] != 0])
             assert not o1.nnz[16:].any() and not o1.level[16:].any() and score >= 0
             seen.update(k for k in cnt)
-    assert {k.split("_")[1] for k in seen} >= ({"dropped", "part", "whole"} if dec else {"whole"}), seen
+    arms = {k.split("_")[1] for k in seen if isinstance(k, str)}     # (the tuple keys count sides of bounds)
+    assert arms >= ({"dropped", "part", "whole"} if dec else {"whole"}), seen
 
 
 # ------------------------------------------------------------------ 2. decoder agreement
@@ -417,6 +418,37 @@ def test_a_wrong_category_changes_the_outputs(bd):
     for kind in ("inter", "intra"):
         for t8 in (False, True):
             assert changed[kind, t8] >= 1, (kind, t8, dict(changed))
+
+
+@pytest.mark.parametrize("bd", [8, 10])
+def test_gpu_keys_reach_the_running_score_on_both_sides_of_6(bd):
+    """over what tests/test_gpu_mb444.py runs with decimation, the score that runs on through the
+    planes ends a plane below 6, above 6 and exactly at 6 with either transform, and the boundary
+    picture has it at 6 after each of the three planes"""
+    seen = set()
+    for key, dec in m4.gpu_keys(bd=bd, dec=1):
+        case, out = m4.make_case(*key), m4.expected(key, dec)
+        for mb, rec in out.rec.items():
+            run = 0
+            for p in range(3):
+                run += rec[p].own
+                if rec[p].nonzero:
+                    seen.add((bool(case.flags[mb] & m4.T8), (run > 6) - (run < 6), key in m4.boundary_keys(), p))
+    for t8 in (False, True):
+        assert {(t8, -1), (t8, 0), (t8, 1)} <= {s[:2] for s in seen}, t8
+        assert {(t8, 0, True, p) for p in range(3)} <= seen, t8
+    # and once through a carry: the 6 is what an earlier plane left plus the plane's own
+    for key in m4.boundary_keys():
+        if key[0] == bd:
+            owns = [[r.own for r in rec] for rec in m4.expected(key, 1).rec.values()]
+            assert any(0 < o[0] and o[1] == 0 and 0 < o[2] < 6 and sum(o) == 6 for o in owns), owns
+
+
+def test_gpu_keys_are_the_groups_of_the_gpu_tests():
+    """the parametrised selections of tests/test_gpu_mb444.py add up to gpu_keys(), nothing twice"""
+    picked = [kd for bd in (8, 10) for dec in (0, 1) for kd in m4.gpu_keys("shapes", bd=bd, dec=dec)]
+    picked += [kd for bd in (8, 10) for kd in m4.gpu_keys("distinct", bd=bd)] + m4.gpu_keys("boundary")
+    assert sorted(map(repr, picked)) == sorted(map(repr, m4.gpu_keys())) and len(set(picked)) == len(picked)
 
 
 def test_case_lists():

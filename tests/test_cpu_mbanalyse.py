@@ -41,15 +41,8 @@ def golden():
 
 def gpu_keys(bd):
     """the keys tests/test_gpu_mbanalyse.py runs at one bit depth"""
-    ks = []
-    for cf in (0, 1, 2):
-        for st in (0, 1, 2):
-            ks += ma.case_keys(bd, cf, st)
-    for kw in (dict(b_i8x8=0), dict(b_i4x4=0), dict(cqm="jvt"), dict(b_chroma_me=1), dict(subme=2)):
-        ks += [ma.make_key(bd, 1, 5, 4, 2, 1, **kw), ma.make_key(bd, 1, 5, 4, 2, 0, **kw), ma.make_key(bd, 2, 5, 4, 2, 2, **kw)]
-    for content in ("flat", "checker"):
-        ks += [ma.make_key(bd, 1, 5, 4, 1, 0, content=content), ma.make_key(bd, 2, 3, 2, 1, 1, content=content)]
-    return ks
+    ks = [key for key, _ in ma.gpu_keys(bd=bd)]
+    return sorted(set(ks), key=ks.index)
 
 
 # ------------------------------------------------------------------ 1. the tables
@@ -299,6 +292,45 @@ def test_coverage_of_the_gpu_inputs(bd):
         assert all(c["chosenc", m] for m in range(7)), cf
         assert c["chroma_x3"] and c["chroma_list"]
         assert all(c["decided", st, kind] for st in (0, 1) for kind in ("i16", "i8", "i4")), cf
+
+
+BOUNDS = (("chroma_list_cost",), ("chroma_x3_cost",), ("i16_x3_cost",), ("i16_plane_cost",), ("i16_cost",), ("i8_best",),
+          ("i8_gate",), ("type_i", "i4"), ("type_i", "i8"), ("type_pb", "i4"), ("type_pb", "i8"))
+RUNNING = ("i4_cost", "i8_cost")                                     # (bound, side, at the last block)
+
+
+@pytest.mark.parametrize("bd", [8, 10])
+def test_gpu_keys_reach_every_bound_on_both_sides(bd):
+    """over exactly what tests/test_gpu_mbanalyse.py runs at this depth, each cost the reference
+    compares with a threshold or with another cost is seen below it, above it and exactly on it"""
+    tot = collections.Counter()
+    for key, dec in ma.gpu_keys(bd=bd):
+        tot.update(ma.expected(key, dec).counters)
+    for b in BOUNDS:
+        assert tot[b + ("below",)] and tot[b + ("above",)], b
+        assert tot[b + ("at",)], b
+    for b in RUNNING:                                                # before the last block, where the loop can still stop
+        assert tot[b, "below", 0] and tot[b, "at", 0] and tot[b, "above", 0], b
+    assert tot["type_pb", "i16", "below"] and tot["type_pb", "i16", "above"]
+
+
+@pytest.mark.parametrize("bd", [8, 10])
+def test_every_boundary_picture_sits_on_its_bound(bd):
+    """each picture of BOUNDARY, at each depth, has the comparison it is named for at equality"""
+    for row, (what, at, _, _) in enumerate(ma.BOUNDARY):
+        assert ma.expected(ma.boundary_key(bd, row), 1).counters[at] > 0, (bd, what)
+
+
+def test_gpu_keys_are_the_groups_of_the_gpu_tests():
+    """the parametrised selections of tests/test_gpu_mbanalyse.py add up to gpu_keys()"""
+    picked = [kd for bd in (8, 10) for cf in (0, 1, 2) for st in (0, 1, 2) for kd in ma.gpu_keys("shapes", bd=bd, cf=cf, slice_type=st)]
+    picked += [kd for bd in (8, 10) for kw in ma.OPTIONS for kd in ma.gpu_keys("options", bd=bd, **kw)]
+    picked += [kd for bd in (8, 10) for c in ("flat", "checker") for kd in ma.gpu_keys("content", bd=bd, content=c)]
+    picked += [kd for bd in (8, 10) for st in (0, 1) for kd in ma.gpu_keys("noise", bd=bd, slice_type=st)]
+    picked += [kd for bd in (8, 10) for kd in ma.gpu_keys("boundary", bd=bd)]
+    assert sorted(map(repr, picked)) == sorted(map(repr, ma.gpu_keys()))
+    for key, _ in ma.gpu_keys("boundary"):
+        assert key[2] <= 5 and key[3] <= 4 and key[4] <= 2
 
 
 @pytest.mark.parametrize("bd", [8, 10])

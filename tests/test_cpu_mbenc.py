@@ -171,6 +171,42 @@ def test_case_lists_reach_every_branch(bd, cf):
     assert differs >= 1
 
 
+@pytest.mark.parametrize("bd", [8, 10])
+def test_gpu_keys_reach_every_bound_on_both_sides(bd):
+    """over what tests/test_gpu_mbenc.py runs, every bound of the reference the checker restates is
+    met from below, from above and exactly: the decimate scores 4 / 6 (both transforms) and 7
+    (chroma), chroma qp 18, var2 against 4 * thresh, ssd against thresh, dmf against 32 * 64; and
+    the exact hits are the boundary pictures' own"""
+    cnt, own = collections.Counter(), collections.Counter()
+    for key, dec in mc.gpu_keys(bd=bd, dec=1):
+        cnt.update(mc.expected(key, dec).counters)
+        if key in mc.boundary_keys():
+            own.update(mc.expected(key, dec).counters)
+    bounds = [(t, b) for t in ("4", "8") for b in ("score8x8", "score_mb")]
+    bounds += [("4", b) for b in ("score_chroma", "chroma_qp", "var2", "ssd", "dmf")]
+    for tag, b in bounds:
+        for side in ("below", "at", "above"):
+            assert cnt[(tag, (b, side))] > 0, (tag, b, side)
+        assert own[(tag, (b, "at"))] > 0, (tag, b)
+    for cf in (1, 2):                                                # the early-out's equalities in each chroma format
+        at = collections.Counter()
+        for key in mc.boundary_keys():
+            if key[0] == bd and key[1] == cf:
+                at.update(mc.expected(key, 1).counters)
+        for b in ("score_chroma", "chroma_qp", "var2", "ssd", "dmf"):
+            assert at[("4", (b, "at"))] > 0, (cf, b)
+
+
+def test_gpu_keys_are_the_groups_of_the_gpu_tests():
+    """the parametrised selections of tests/test_gpu_mbenc.py add up to gpu_keys(), nothing twice"""
+    picked = [kd for bd in (8, 10) for cf in (0, 1, 2) for dec in (0, 1) for kd in mc.gpu_keys("shapes", bd=bd, cf=cf, dec=dec)]
+    picked += [kd for bd in (8, 10) for cf in (1, 2) for kd in mc.gpu_keys("jvt", bd=bd, cf=cf)]
+    picked += mc.gpu_keys("boundary")
+    assert sorted(map(repr, picked)) == sorted(map(repr, mc.gpu_keys())) and len(set(picked)) == len(picked)
+    for key, _ in mc.gpu_keys("boundary"):
+        assert key[2] * key[3] * key[4] <= 40 and key[2] <= 5 and key[3] <= 4
+
+
 def test_case_lists_mix_every_kind_of_macroblock():
     case = mc.make_case(8, 1, 5, 4, 2)
     fl = case.flags

@@ -222,10 +222,8 @@ LISTS = [(bd, cf) for bd in (8, 10) for cf in (0, 1, 2)]
 
 def gpu_keys(bd, cf):
     """every key tests/test_gpu_mbintra.py runs at this bit depth and chroma format"""
-    keys = mi.case_keys(bd, cf) + [mi.all_intra_key(bd, cf)]
-    if cf:
-        keys.append((bd, cf, 5, 4, 2, "jvt", 0, False))
-    return keys
+    keys = [key for key, _ in mi.gpu_keys(bd=bd, cf=cf)]
+    return sorted(set(keys), key=keys.index)
 
 
 @pytest.mark.parametrize("bd,cf", LISTS)
@@ -263,6 +261,12 @@ def test_inputs_reach_every_branch(cf):
     for arm in ("i16_idct_dc", "i16_idct_nodc", "i16_dc_only", "i16_pred_only"):
         assert both[arm], arm
     assert cnt[1]["i16_decimated"] and not cnt[0]["i16_decimated"]
+    own = collections.Counter()
+    for key in mi.boundary_keys():
+        if key[1] == cf:
+            own.update(mi.expected(key, 1).counters)
+    for side in ("below", "at", "above"):                            # the AC decimate score against 6
+        assert cnt[1]["i16_score", side] and own["i16_score", side], side
     for tail in ("chroma_empty", "chroma_dconly", "chroma_dcac") if cf else ():
         assert both[tail], tail
     assert both["topright_emulated"] and both["topright_real"]
@@ -272,6 +276,16 @@ def test_inputs_reach_every_branch(cf):
     assert both["intra_coded"] * 10 >= both["intra"] > 0
     for t in ("i4", "i8", "i16"):
         assert both["type", t], t
+
+
+def test_gpu_keys_are_the_groups_of_the_gpu_tests():
+    """the parametrised selections of tests/test_gpu_mbintra.py add up to gpu_keys(), nothing twice"""
+    grid = [(bd, cf, dec) for bd in (8, 10) for cf in (0, 1, 2) for dec in (0, 1)]
+    picked = [kd for bd, cf, dec in grid for kd in mi.gpu_keys("shapes", bd=bd, cf=cf, dec=dec)]
+    picked += [kd for bd in (8, 10) for cf in (1, 2) for kd in mi.gpu_keys("jvt", bd=bd, cf=cf)]
+    picked += [kd for bd in (8, 10) for cf in (0, 1, 2) for kd in mi.gpu_keys("all_intra", bd=bd, cf=cf)]
+    picked += mi.gpu_keys("boundary")
+    assert sorted(map(repr, picked)) == sorted(map(repr, mi.gpu_keys())) and len(set(picked)) == len(picked)
 
 
 def test_case_lists():

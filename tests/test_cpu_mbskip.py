@@ -433,3 +433,30 @@ def test_wrapper_refusals_need_no_device():
         x.mb_skip_convert(sk, torch.zeros(1, dtype=torch.int32), 1, 1)
     with pytest.raises(ValueError, match="cbp must be"):
         x.mb_skip_convert(sk, torch.zeros(1, dtype=torch.int16), 1, 1, b_bframe=True, direct=sk)
+
+
+# ------------------------------------------------------------------ the boundary macroblocks
+@pytest.mark.parametrize("bd", [8, 10])
+def test_boundary_macroblocks_meet_the_probe_thresholds(bd):
+    """at each depth the pictures of mbskip_cases.BOUNDARY by themselves tell the luma bound 6, the
+    chroma AC bound 7 and `ssd < thresh` (at 4:2:0 and at 4:2:2), flipped at their boundary
+    (tests/mutants.py), from the checker; and the macroblock next to the luma one skips at 3"""
+    import mutants as mu
+    keys = [k for k in ms.boundary_keys() if k[0] == bd]
+    for text, cfs in (("i_decimate_mb >= 6", (0, 1, 2)), ("i_decimate_mb >= 7", (1, 2)), ("ssd < thresh", (1, 2))):
+        (site,) = [s for s in mu.sites("mbskip_cases") if s.func == "probe_literal" and s.text == text]
+        m = mu.load("mbskip_cases", site.index)
+        for cf in cfs:
+            mine = [k for k in keys if k[1] == cf]
+            assert any(not np.array_equal(m.expected(k)[0], ms.expected(k)[0]) for k in mine), (bd, text, cf)
+    for k in keys:
+        if k[6] == "flat":
+            assert ms.expected(k)[0][:2].tolist() == [1, 0], k
+
+
+def test_gpu_keys_are_the_groups_of_the_gpu_tests():
+    """the parametrised selections of tests/test_gpu_mbskip.py add up to gpu_keys(), nothing twice"""
+    picked = [e for sh in ms.SHAPES for e in ms.gpu_keys("pskip", shape=sh)]
+    picked += [e for bd in (8, 10) for cf in (0, 1, 2, 3) for leg in ms.LEGS for e in ms.gpu_keys("probe", bd=bd, cf=cf, leg=leg)]
+    picked += [e for bf in (0, 1) for e in ms.gpu_keys("convert", bframe=bf)] + ms.gpu_keys("boundary")
+    assert sorted(map(repr, picked)) == sorted(map(repr, ms.gpu_keys())) and len(set(picked)) == len(picked)

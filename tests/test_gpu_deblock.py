@@ -78,12 +78,12 @@ def _same(got, want):
 
 
 # ------------------------------------------------------------------ 1. the picture
-@pytest.mark.parametrize("key", dc.MAIN + dc.FORMATS + dc.SHAPES + dc.FRAMES + dc.LONG + dc.TOP, ids=dc.case_id)
+@pytest.mark.parametrize("key", [e[1] for e in dc.gpu_keys("frames")], ids=dc.case_id)
 def test_deblock_frames(hip, key):
     _same(_gpu(hip, dc.make_case(*key)), dc.expected(key))
 
 
-@pytest.mark.parametrize("key", dc.LOW_QP, ids=dc.case_id)
+@pytest.mark.parametrize("key", [e[1] for e in dc.gpu_keys("low_qp")], ids=dc.case_id)
 def test_low_qp_changes_nothing(hip, key):
     """qp 0..15: qp <= qp_thresh and alpha = 0 -- nothing changes, as the checker says"""
     c = dc.make_case(*key)
@@ -92,7 +92,7 @@ def test_low_qp_changes_nothing(hip, key):
     _same(_gpu(hip, c), want)
 
 
-@pytest.mark.parametrize("key", dc.SLICES, ids=dc.case_id)
+@pytest.mark.parametrize("key", [e[1] for e in dc.gpu_keys("slices")], ids=dc.case_id)
 def test_slices(hip, key):
     """two slices split mid-row: the edges across the split are untouched; the same call with NULL
     filters them"""
@@ -144,14 +144,30 @@ def _strength_gpu(hip, s, mvy_limit):
 
 @pytest.mark.parametrize("mvy_limit", [4, 2])
 @pytest.mark.parametrize("bframe", [False, True], ids=["P", "B"])
-@pytest.mark.parametrize("shape", [(5, 4, 2), (24, 14, 1)], ids=["5x4x2", "24x14x1"])
+@pytest.mark.parametrize("shape", dc.STRENGTH_SHAPES, ids=["5x4x2", "24x14x1"])
 def test_deblock_strength(hip, shape, bframe, mvy_limit):
+    assert ("strength", shape + (bframe,), mvy_limit) in dc.gpu_keys("strength")
     s = dc.make_strength_case(*shape, bframe)
     want = dc.deblock_strength_py(s.nz, s.mb_flags, s.mv, s.ref, s.mbw, s.mbh, s.nf, mvy_limit)
     got = _strength_gpu(hip, s, mvy_limit)
     bad = np.argwhere(got != want)
     assert not len(bad), "%d of %d strengths differ, first at (mb, dir, edge, i) %s" % (len(bad), want.size, bad[0])
     assert set(np.unique(want)) == {0, 1, 2, 3, 4}
+
+
+@pytest.mark.parametrize("entry", dc.gpu_keys("boundary"),
+                         ids=lambda e: dc.case_id(e[1]) if e[0] == "frames" else "strength-%s-%d" % ("B" if e[1][3] else "P", e[2]))
+def test_boundary_cases_bit_exact(hip, entry):
+    """the pictures of deblock_cases.BOUNDARY -- steps across the edges that equal alpha, beta and
+    (alpha >> 2) + 2 at the foot of the qp range, at both depths and in every chroma layout -- and
+    the small fields of BOUNDARY_STRENGTH with vector steps of exactly the limit: a kernel that
+    takes `<` for `<=` in a line filter, or `>=` for `>` in the strength rule, differs here"""
+    want = dc.gpu_expected(entry)
+    if entry[0] == "frames":
+        _same(_gpu(hip, dc.make_case(*entry[1])), want)
+    else:
+        got = _strength_gpu(hip, dc.make_strength_case(*entry[1]), entry[2])
+        assert np.array_equal(got, want), np.argwhere(got != want)[:4]
 
 
 # ------------------------------------------------------------------ 3. the chain

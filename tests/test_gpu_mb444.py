@@ -177,7 +177,9 @@ def test_mb_encode_444_bit_exact(hip, bd, dec, apart):
     macroblocks per frame) -- as a mixed picture (inter entry, then intra entry) and as an I picture,
     and 1x3x1 and 2x2x1 (one and two macroblocks wide: diagonals that start below row 0) as I
     pictures, flat matrices, the output arrays aligned and one element off"""
-    for i, key in enumerate(k for k in m4.case_keys(bd) if k[4] == "flat"):
+    keys = m4.gpu_keys("shapes", bd=bd, dec=dec)
+    assert len(keys) == 2 * len(m4.SHAPES) - len(m4.I_ONLY_SHAPES)
+    for i, (key, dec) in enumerate(keys):
         run(hip, key, dec, shift=(i + apart) & 1, apart=apart)
         if not apart:
             run(hip, key, dec, shift=(i + 1) & 1, apart=False)
@@ -187,8 +189,20 @@ def test_mb_encode_444_bit_exact(hip, bd, dec, apart):
 def test_mb_encode_444_distinct_matrices(hip, bd):
     """eight pairwise different lists: every plane of every kind of macroblock reads its own
     category (a mixed 7x3x3 and a 5x4x2 I picture)"""
-    for key in m4.DISTINCT_KEYS(bd):
-        run(hip, key, 1, shift=1, apart=False)
+    for key, dec in m4.gpu_keys("distinct", bd=bd):
+        run(hip, key, dec, shift=1, apart=False)
+
+
+@pytest.mark.parametrize("key,dec", m4.gpu_keys("boundary"), ids=lambda v: "%dbit" % v[0] if isinstance(v, tuple) else None)
+def test_boundary_cases_bit_exact(hip, key, dec):
+    """the macroblocks of mb444_cases.BOUNDARY: the decimate score that runs on through the planes is
+    exactly 6 when plane 0, 1 or 2 ends, with either transform; a kernel that drops a plane at 6
+    differs here"""
+    try:
+        run(hip, key, dec, shift=0, apart=False)
+        run(hip, key, dec, shift=1, apart=True)
+    except AssertionError as e:
+        raise AssertionError("%s\nmacroblocks: %s" % (e, [(i, n) for i, (n, _) in enumerate(m4.BOUNDARY)]))
 
 
 # ------------------------------------------------------------------ plain tensors

@@ -154,19 +154,24 @@ def test_mb_analyse_intra_bit_exact(hip, bd, cf, slice_type):
     macroblock with a top-right neighbour), 5x4 x 2 and 7x3 x 3 frames (the x + 2y skew, a frame
     boundary inside a launch, a right edge without top-right) -- with the output arrays aligned
     and one element off, decimation on and off, both arena fills"""
-    for i, key in enumerate(ma.case_keys(bd, cf, slice_type)):
+    entries = ma.gpu_keys("shapes", bd=bd, cf=cf, slice_type=slice_type)
+    keys = sorted(set(k for k, _ in entries), key=[k for k, _ in entries].index)
+    assert len(keys) == len(ma.SHAPES) and all((k, d) in entries for k in keys for d in (0, 1))
+    for i, key in enumerate(keys):
         run(hip, key, dec=i & 1, shift=i & 1, fill=fp.FILLS[i & 1])
         run(hip, key, dec=1 - (i & 1), shift=1 - (i & 1), fill=fp.FILLS[1 - (i & 1)])
 
 
 @pytest.mark.parametrize("bd", [8, 10])
-@pytest.mark.parametrize("kw", [dict(b_i8x8=0), dict(b_i4x4=0), dict(cqm="jvt"), dict(b_chroma_me=1), dict(subme=2)])
+@pytest.mark.parametrize("kw", ma.OPTIONS)
 def test_mb_analyse_intra_options(hip, bd, kw):
     """I_8x8 off, I_4x4 off, the JVT matrices, the chroma-ME leg, i_subpel_refine 2, on a P and an I
     picture at 4:2:0 and a B picture at 4:2:2"""
-    run(hip, ma.make_key(bd, 1, 5, 4, 2, 1, **kw), shift=1)
-    run(hip, ma.make_key(bd, 1, 5, 4, 2, 0, **kw))
-    run(hip, ma.make_key(bd, 2, 5, 4, 2, 2, **kw))
+    (p, dp), (i, di), (b, db) = ma.gpu_keys("options", bd=bd, **kw)
+    assert (p[1], p[5], i[1], i[5], b[1], b[5]) == (1, 1, 1, 0, 2, 2)
+    run(hip, p, dec=dp, shift=1)
+    run(hip, i, dec=di)
+    run(hip, b, dec=db)
 
 
 @pytest.mark.parametrize("bd", [8, 10])
@@ -174,8 +179,9 @@ def test_mb_analyse_intra_options(hip, bd, kw):
 def test_flat_and_checkerboard(hip, bd, content):
     """a flat picture (every cost a tie) and a full-scale checkerboard (the top of the cost range)
     at qp 0 and QP_MAX_SPEC"""
-    run(hip, ma.make_key(bd, 1, 5, 4, 1, 0, content=content))
-    run(hip, ma.make_key(bd, 2, 3, 2, 1, 1, content=content))
+    (a, da), (b, db) = ma.gpu_keys("content", bd=bd, content=content)
+    run(hip, a, dec=da)
+    run(hip, b, dec=db)
 
 
 @pytest.mark.parametrize("bd", [8, 10])
@@ -184,7 +190,20 @@ def test_noise_over_what_may_not_be_read(hip, bd, slice_type):
     """pred_mode / chroma_pred_mode of the try macroblocks, satd_inter where it is not read and
     fast_intra of the other macroblocks hold noise: the bytes are those of the clean run, the
     noise of the macroblocks that stay inter still in place"""
-    run(hip, ma.make_key(bd, 1, 5, 4, 2, slice_type), noise=True, shift=1, fill=fp.FILLS[1])
+    (key, dec), = ma.gpu_keys("noise", bd=bd, slice_type=slice_type)
+    run(hip, key, dec=dec, noise=True, shift=1, fill=fp.FILLS[1])
+
+
+@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("what", [b[0] for b in ma.BOUNDARY], ids=lambda w: w.split(":")[0].replace(" ", "_")[:48])
+def test_boundary_cases_bit_exact(hip, bd, what):
+    """the pictures of mbanalyse_cases.BOUNDARY: a cost exactly on the fast-intra gate, the Plane
+    gate, the I_8x8 bound, an early termination or another type's cost, chroma modes that tie: a
+    kernel that ties one of these the other way differs here, in cost[] at the least"""
+    key = ma.boundary_key(bd, [b[0] for b in ma.BOUNDARY].index(what))
+    (key, dec), = [kd for kd in ma.gpu_keys("boundary", bd=bd) if kd[0] == key]
+    run(hip, key, dec=dec, shift=0)
+    run(hip, key, dec=dec, shift=1, fill=fp.FILLS[1])
 
 
 @pytest.mark.parametrize("bd", [8, 10])

@@ -174,7 +174,9 @@ def test_mb_encode_inter_bit_exact(hip, bd, cf, dec):
     """every shape of the case list: 1x1 and 3x1 (a partly filled wave), 5x4 x 2 frames (mixed flags
     inside a wave, a frame stride, a last workgroup half full), 24x14 x 2 frames (many workgroups);
     recon apart from pred with aligned arrays, and in place with the arrays one element off"""
-    for key in mc.case_keys(bd, cf):
+    keys = mc.gpu_keys("shapes", bd=bd, cf=cf, dec=dec)
+    assert len(keys) == len(mc.SHAPES)
+    for key, dec in keys:
         run(hip, key, dec, alias=False, shift=0)
         run(hip, key, dec, alias=True, shift=1)
 
@@ -183,7 +185,20 @@ def test_mb_encode_inter_bit_exact(hip, bd, cf, dec):
 @pytest.mark.parametrize("cf", [1, 2])
 def test_mb_encode_inter_custom_matrices(hip, bd, cf):
     """the JVT matrices: the luma, chroma and 8x8 lists differ from each other"""
-    run(hip, (bd, cf, 5, 4, 2, "jvt", 0), 1, alias=False, shift=1)
+    (key, dec), = mc.gpu_keys("jvt", bd=bd, cf=cf)
+    run(hip, key, dec, alias=False, shift=1)
+
+
+@pytest.mark.parametrize("key,dec", mc.gpu_keys("boundary"), ids=lambda v: "%dbit-cf%d-%s" % (v[0], v[1], v[5]) if isinstance(v, tuple) else None)
+def test_boundary_cases_bit_exact(hip, key, dec):
+    """the macroblocks of mbenc_cases.BOUNDARY, each with one comparison of the reference exactly on
+    its bound (a decimate score of 4 / 6 / 7, chroma qp 18, var2 and ssd on the early-out's
+    thresholds, dmf = 32 * 64): a kernel that ties one of them the other way differs here"""
+    try:
+        run(hip, key, dec, alias=False, shift=0)
+        run(hip, key, dec, alias=True, shift=1)
+    except AssertionError as e:
+        raise AssertionError("%s\nmacroblocks: %s" % (e, list(enumerate(mc.boundary_recipe(key[1], key[5])[3]))))
 
 
 # ------------------------------------------------------------------ plain tensors

@@ -179,7 +179,9 @@ def test_mb_encode_intra_bit_exact(hip, bd, cf, dec):
     intra; 5x4 x 2 frames (mixed inter and intra after mb_encode_inter, a frame stride, the x + 2y
     skew, a right edge without top-right), 24x14 x 2 frames (many workgroups, 50 launches) -- with
     the output arrays aligned and one element off"""
-    for key in mi.case_keys(bd, cf):
+    keys = mi.gpu_keys("shapes", bd=bd, cf=cf, dec=dec)
+    assert len(keys) == len(mi.SHAPES)
+    for key, dec in keys:
         run(hip, key, dec, shift=0)
         run(hip, key, dec, shift=1)
 
@@ -189,15 +191,29 @@ def test_mb_encode_intra_bit_exact(hip, bd, cf, dec):
 def test_mb_encode_intra_custom_matrices(hip, bd, cf):
     """the JVT matrices: the intra luma, intra chroma and 8x8 lists differ from each other and from
     the inter ones"""
-    run(hip, (bd, cf, 5, 4, 2, "jvt", 0, False), 1, shift=1)
+    (key, dec), = mi.gpu_keys("jvt", bd=bd, cf=cf)
+    run(hip, key, dec, shift=1)
 
 
 @pytest.mark.parametrize("bd", [8, 10])
 @pytest.mark.parametrize("cf", [0, 1, 2])
 def test_all_intra_picture(hip, bd, cf):
     """an I picture, 5x4, with no inter call before it; its two last macroblock rows are quiet"""
-    run(hip, mi.all_intra_key(bd, cf), 1, shift=0)
-    run(hip, mi.all_intra_key(bd, cf), 0, shift=1)
+    (k1, d1), (k0, d0) = mi.gpu_keys("all_intra", bd=bd, cf=cf)
+    assert (d1, d0) == (1, 0)
+    run(hip, k1, d1, shift=0)
+    run(hip, k0, d0, shift=1)
+
+
+@pytest.mark.parametrize("key,dec", mi.gpu_keys("boundary"), ids=lambda v: "%dbit-cf%d" % v[:2] if isinstance(v, tuple) else None)
+def test_boundary_cases_bit_exact(hip, key, dec):
+    """the macroblocks of mbintra_cases.BOUNDARY: the AC decimate score of an I_16x16 macroblock
+    below, exactly at and above 6; a kernel that decimates at 6 differs here"""
+    try:
+        run(hip, key, dec, shift=0)
+        run(hip, key, dec, shift=1)
+    except AssertionError as e:
+        raise AssertionError("%s\nmacroblocks: %s" % (e, [(i, n) for i, (n, _) in enumerate(mi.BOUNDARY)]))
 
 
 # ------------------------------------------------------------------ plain tensors

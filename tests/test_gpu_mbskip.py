@@ -89,6 +89,7 @@ def test_mb_predict_mv_pskip_bit_exact(hip, shape):
     """random fields: mixed partitions, refs -1..2, zero vectors, intra macroblocks"""
     import torch
     mbw, mbh, nf = shape
+    assert [e[2] for e in ms.gpu_keys("pskip", shape=shape)] == list(range(len(FILLS)))
     for seed, fill in enumerate(FILLS):
         mv0, ref0 = ms.make_field(mbw, mbh, nf, seed)
         ins = Inputs()
@@ -149,9 +150,23 @@ def test_mb_probe_skip_bit_exact(hip, bd, cf, leg):
     results of a wave stored as one dword) and one and three bytes off (stored one by one); the
     cases hold full-scale checker residuals at qp 0 and QP_MAX_SPEC and, at the four corners of
     every frame, skip vectors beyond mv_max / below mv_min"""
-    for i, key in enumerate(ms.case_keys(bd, cf, leg)):
+    keys = [e[1] for e in ms.gpu_keys("probe", bd=bd, cf=cf, leg=leg)]
+    assert len(keys) == len(ms.SHAPES) + 1
+    for i, key in enumerate(keys):
         run_probe(hip, key, FILLS[0], 0)
         run_probe(hip, key, FILLS[1], 1 + 2 * (i & 1))
+
+
+@pytest.mark.parametrize("key", [e[1] for e in ms.gpu_keys("boundary")], ids=lambda k: "%dbit-cf%d-%s" % (k[0], k[1], k[6]))
+def test_boundary_cases_bit_exact(hip, key):
+    """the macroblocks of mbskip_cases.BOUNDARY on the B leg: a luma score of exactly 6, a chroma AC
+    score of exactly 7, a chroma ssd of exactly thresh whose DC still quantises to a level; a kernel
+    that ties one of the probe's thresholds the other way answers differently here"""
+    try:
+        run_probe(hip, key, FILLS[0], 0)
+        run_probe(hip, key, FILLS[1], 1)
+    except AssertionError as e:
+        raise AssertionError("%s\nmacroblocks: %s" % (e, [b[0] for b in ms.BOUNDARY if key[1] in b[1] and (b[3:] or ("flat",))[0] == key[6]]))
 
 
 # ------------------------------------------------------------------ the conversion
@@ -159,7 +174,9 @@ def test_mb_probe_skip_bit_exact(hip, bd, cf, leg):
 @pytest.mark.parametrize("bframe", [0, 1])
 def test_mb_skip_convert_bit_exact(hip, bframe, alias):
     import torch
-    for shape in ms.SHAPES:
+    shapes = [e[1] for e in ms.gpu_keys("convert", bframe=bframe)]
+    assert shapes == list(ms.SHAPES)
+    for shape in shapes:
         c = ms.make_convert_case(*shape, bframe)
         want = ms.skip_convert(c.flags, c.cbp, c.mv0, c.ref0, c.pskip, bframe, c.direct, c.mbw, c.mbh)
         for k, fill in enumerate(FILLS):
